@@ -23,8 +23,21 @@ bytes are all-gathered once after the timed steps (RCCL over xGMI).
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with a
 ``roofline`` object for the dominant kernel (the vocoder's implicit-GEMM MFMA conv,
-timed live with HIP events on its stream) and a ``cpu_baseline`` object (the oracle's
-CPU restatement on a bounded sample, rank 0 at N=1 only).
+timed live with HIP events on its stream).
+
+A plain run does only what the headline needs: set-up, priming and warm-up, the --steps
+timed steps, the --dump-outputs files, the line. --full adds every measurement that takes
+work of its own after the timed region (their keys are null on a plain line): the
+idle-pipeline and overlapped latency legs, the first-window and temperature-fallback legs,
+the host edges, the ``cpu_baseline`` object (the oracle's CPU restatement on a bounded
+sample, rank 0 at N=1 only), config 3's per-kernel lines and config 5's T = 0 leg.
+
+--dump-outputs DIR (config 4, rank 0): what the last timed step returned, as float32
+DIR/<name>.npy: ``tokens`` [B][max_length] and ``n_tokens`` [B] (first-window decode),
+``stats`` [B][3] (rms, mean voiced f0, voiced hops), and ``wav`` / ``pcm16``, the rendered
+batch at DUMP_SAMPLES seeded positions (``sample_index`` holds them). Inputs and weights
+are seeded, so two builds run with the same arguments compare file for file. Packets are
+left out: they carry the wall-clock timestamp.
 """
 import argparse
 import json
@@ -53,7 +66,15 @@ def parse():
     ap.add_argument("--seconds", type=float, default=AUDIO_SECONDS)
     ap.add_argument("--model", default="base.en")
     ap.add_argument("--max-length", type=int, default=448)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the latency, "
+                         "first-window and fallback legs, the host edges, the CPU baseline, "
+                         "config 3's per-kernel lines, config 5's T = 0 leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config 4: write what the last timed step returned to DIR/<name>.npy "
+                         "(float32; wav and pcm16 at a fixed seeded sample of positions)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--overlap", type=int, default=int(os.environ.get("JANUS_OVERLAP", "16")),
                     help="CUs per XCD (of 32) for the greedy decoder in the overlapped serving step "
                          "(vocoder of batch i-1 on the rest; multiples of 4 keep every shader engine "
@@ -100,7 +121,38 @@ def parse():
                     help="run faster-whisper's temperature fallback on windows failing their gates "
                          "(generate_with_fallback: 5 temperatures x best_of 5 sampled re-decodes); "
                          "off by default: the seeded synthetic weights fail every window (DESIGN.md §0)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and (args.config != 4 or args.launch_check):
+        ap.error("--dump-outputs belongs to the headline configuration (--config 4)")
+    if not args.full:   # a plain run: the timed steps and the line, none of the legs after them
+        args.no_cpu_baseline = args.no_idle_latency = True
+        args.fallback_steps = args.first_window_steps = 0
+    return args
+
+
+DUMP_SAMPLES = 1 << 21          # wav / pcm16 positions kept by --dump-outputs (8 MiB each)
+
+
+def dump_outputs(path, enc, wav, pcm16):
+    """--dump-outputs: the arrays of one step's (EncodeResult, wav, pcm16) as float32 .npy
+    files under ``path``; wav and pcm16 at the same DUMP_SAMPLES positions (seed 0, sorted)
+    when they hold more."""
+    os.makedirs(path, exist_ok=True)
+    out = {"tokens": enc.tokens.cpu().numpy(), "n_tokens": enc.n_tokens.cpu().numpy()}
+    if enc.stats is not None:
+        out["stats"] = enc.stats.cpu().numpy()
+    if wav is not None:
+        n = wav.numel()
+        if n > DUMP_SAMPLES:
+            idx = np.sort(np.random.default_rng(0).integers(0, n, DUMP_SAMPLES))
+            out["sample_index"] = idx
+            idx = torch.from_numpy(idx).to(wav.device)
+            wav, pcm16 = wav.reshape(-1)[idx], pcm16.reshape(-1)[idx]
+        out["wav"], out["pcm16"] = wav.cpu().numpy(), pcm16.cpu().numpy()
+    for name, a in out.items():
+        # float32 holds token ids, counts and int16 exactly; flat positions need float64
+        np.save(os.path.join(path, name + ".npy"),
+                a.astype(np.float64 if name == "sample_index" else np.float32))
 
 
 def cpu_baseline(model: str, tokens_per_utt: float, seed: int = 999, windows: float = 1.0):
@@ -418,10 +470,8 @@ def encoder_flops(cfg, B):
 def run_config3(args):
     """BASELINE config 3: base.en encode-only (log-mel + encoder: conv stem, 6 layers of
     MFMA attention / FFN) on 64 x 30 s utterances; xRT and the encoder's MFMA fraction,
-    plus per-kernel lines for the projection GEMM (gemm_big) and the attention kernel at
-    the same shapes (HIP events)."""
-    import math
-    from janus_amd import _native as nat
+    plus, with --full, per-kernel lines for the projection GEMM (gemm_big) and the
+    attention kernel at the same shapes (HIP events)."""
     from janus_amd.whisper import CONFIGS, WhisperEngine
     from janus_amd.workload import synth_speech
     dev = torch.device("cuda", 0)
@@ -458,7 +508,34 @@ def run_config3(args):
     fl = encoder_flops(cfg, B)
     tot = sum(fl.values())
     ach = tot / (enc_ms * 1e-3) / 1e12
-    # the encoder's kernels at the same shapes, alone (kernel ABI, HIP events)
+    kern = encoder_kernel_lines(cfg, B, dev) if args.full else None
+    step_s = (mel_ms + enc_ms) / 1000.0
+    cpu = None
+    if not args.no_cpu_baseline:
+        try:
+            cpu = cpu_encoder_baseline(args.model)
+        except Exception as e:
+            cpu = {"error": repr(e)}
+    _line(args, "config 3: base.en encode-only, batch 64 x 30 s, xRT and MFMA fraction",
+          B * args.seconds / step_s, "xRT (audio-s/wall-s)", step_s * 1000.0,
+          {"workload": f"log-mel + {args.model} encoder, {B} x {args.seconds:g} s", "model": args.model,
+           "global_batch": B, "seq_len": cfg.n_audio_ctx},
+          mel_ms=round(mel_ms, 3), encoder_ms=round(enc_ms, 3),
+          host_step_ms=[round(v * 1000.0, 2) for v in t],
+          roofline={"kernel": "Whisper encoder forward (stem conv, QKV/O/fc1/fc2 on gemm_big, "
+                              "attention_st), HIP events around the encoder",
+                    "bound": "mfma", "achieved": round(ach, 1), "peak": MFMA_F16_PEAK_TFLOPS,
+                    "unit": "TFLOP/s", "frac": round(ach / MFMA_F16_PEAK_TFLOPS, 4),
+                    "traffic": None, "flops": {k: float(v) for k, v in fl.items()},
+                    "kernels": kern},
+          cpu_baseline=cpu)
+
+
+def encoder_kernel_lines(cfg, B, dev):
+    """Config 3 with --full: the encoder's kernels at the same shapes, alone (kernel ABI,
+    HIP events): one line each for the projection GEMMs and the attention kernel."""
+    import math
+    from janus_amd import _native as nat
     s = torch.cuda.current_stream().cuda_stream
     M, d = B * cfg.n_audio_ctx, cfg.d_model
     kern = []
@@ -501,26 +578,7 @@ def run_config3(args):
     kern.append({"kernel": f"attention_st ({B} x {cfg.n_heads} heads x {cfg.n_audio_ctx}^2)",
                  "us": round(us, 1), "achieved_tflops": round(tf, 1),
                  "frac": round(tf / MFMA_F16_PEAK_TFLOPS, 4)})
-    step_s = (mel_ms + enc_ms) / 1000.0
-    cpu = None
-    if not args.no_cpu_baseline:
-        try:
-            cpu = cpu_encoder_baseline(args.model)
-        except Exception as e:
-            cpu = {"error": repr(e)}
-    _line(args, "config 3: base.en encode-only, batch 64 x 30 s, xRT and MFMA fraction",
-          B * args.seconds / step_s, "xRT (audio-s/wall-s)", step_s * 1000.0,
-          {"workload": f"log-mel + {args.model} encoder, {B} x {args.seconds:g} s", "model": args.model,
-           "global_batch": B, "seq_len": cfg.n_audio_ctx},
-          mel_ms=round(mel_ms, 3), encoder_ms=round(enc_ms, 3),
-          host_step_ms=[round(v * 1000.0, 2) for v in t],
-          roofline={"kernel": "Whisper encoder forward (stem conv, QKV/O/fc1/fc2 on gemm_big, "
-                              "attention_st), HIP events around the encoder",
-                    "bound": "mfma", "achieved": round(ach, 1), "peak": MFMA_F16_PEAK_TFLOPS,
-                    "unit": "TFLOP/s", "frac": round(ach / MFMA_F16_PEAK_TFLOPS, 4),
-                    "traffic": None, "flops": {k: float(v) for k, v in fl.items()},
-                    "kernels": kern},
-          cpu_baseline=cpu)
+    return kern
 
 
 def cpu_encoder_baseline(model):
@@ -555,9 +613,11 @@ def run_config5(args, rank, world, use_dist, dev):
     all-gathered (RCCL), so rank 0 reports the node's p50 / p99 and whether every block
     and phrase stayed inside the 320 ms block. Two legs, the same channels: faster-whisper's
     temperature fallback (the reference's transcribe_buffer, engine.py:510-527: the line's
-    value) and T = 0 alone (``t0``); --stream-t0 runs the T = 0 leg only."""
+    value) and, with --full, T = 0 alone (``t0``); --stream-t0 runs the T = 0 leg only."""
     from janus_amd.services.transcriber import TEMPERATURES
-    legs = [("t0", (0.0,))] if args.stream_t0 else [("fallback", TEMPERATURES), ("t0", (0.0,))]
+    legs = [("t0", (0.0,))] if args.stream_t0 else [("fallback", TEMPERATURES)]
+    if args.full and not args.stream_t0:
+        legs.append(("t0", (0.0,)))
     res = {name: _stream_leg(args, rank, world, use_dist, dev, temps) for name, temps in legs}
     if rank != 0:
         return
@@ -766,6 +826,8 @@ def main():
         else:
             enc, wav, pcm16 = pipe.step(pcm, offs, lengths, frames)
         last["pcm16"] = pcm16
+        if args.dump_outputs:
+            last["wav"] = wav
         return enc
 
     # priming: the pipeline's depth in steps (staggered: until the first batch comes out,
@@ -806,6 +868,8 @@ def main():
         dist.barrier()
     t_end = time.perf_counter()
     pipe.vocoder.set_timing(False)
+    if args.dump_outputs and rank == 0:   # before any later leg steps the pipeline again
+        dump_outputs(args.dump_outputs, enc, last.get("wav"), last.get("pcm16"))
     yin_dec_utts = (getattr(pipe, "_stag", None) or {}).get("n_dec") if args.stagger == 1 else None
     # rows per decoder call: every slot set's R rows (R = 2B with all windows)
     dec_rows = sets * ((getattr(pipe, "_stag", None) or {}).get("R", B) if args.stagger else B)
@@ -904,20 +968,22 @@ def main():
         # stats (rms, mean f0, voiced hops) on every rank, untimed
         pk_all, st_all = gather_results(enc.packets, enc.stats, dev)
         n_packets, n_stats = sum(p is not None for p in pk_all), int(st_all.shape[0])
-    # host edges, outside the timed region (value has inputs resident in HBM): the PCM
+    # host edges (--full), outside the timed region (value has inputs resident in HBM): the PCM
     # upload of a batch and the download + RIFF framing of its int16 waveforms
-    from janus_amd.vocoder import wav_bytes
-    host_pcm = np.concatenate(utts + [np.zeros(1, np.float32)])
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    _ = torch.from_numpy(host_pcm).to(dev)
-    torch.cuda.synchronize()
-    t_up = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    if last.get("pcm16") is not None:
-        h16 = last["pcm16"].cpu().numpy()
-        _ = [wav_bytes(r) for r in h16]
-    t_down = time.perf_counter() - t0
+    t_up = t_down = None
+    if args.full:
+        from janus_amd.vocoder import wav_bytes
+        host_pcm = np.concatenate(utts + [np.zeros(1, np.float32)])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _ = torch.from_numpy(host_pcm).to(dev)
+        torch.cuda.synchronize()
+        t_up = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        if last.get("pcm16") is not None:
+            h16 = last["pcm16"].cpu().numpy()
+            _ = [wav_bytes(r) for r in h16]
+        t_down = time.perf_counter() - t0
     wall = float(total_t.item())
     ms_per_step = wall / args.steps * 1000.0
     audio_s = world * B * args.seconds
@@ -1014,8 +1080,10 @@ def main():
             "xrt_with_fallback": fb["xrt"] if fb else None,
             "fallback": fb,
             "host_edges_ms": {"pcm_upload": round(t_up * 1000.0, 1),
-                              "wav_download_and_framing": round(t_down * 1000.0, 1)},
-            "xrt_incl_host_edges": round(audio_s / (wall / args.steps + t_up + t_down), 2),
+                              "wav_download_and_framing": round(t_down * 1000.0, 1)}
+            if args.full else None,
+            "xrt_incl_host_edges": round(audio_s / (wall / args.steps + t_up + t_down), 2)
+            if args.full else None,
             "roofline": {
                 "kernel": "conv1d implicit-GEMM (vocoder, v_mfma_f32_16x16x32_f16)",
                 "bound": "mfma",

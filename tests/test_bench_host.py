@@ -47,6 +47,53 @@ def test_encoder_flops_base_en(bench):
     assert abs(sum(fl.values()) / 1e9 - 87.3) < 0.2
 
 
+def test_plain_run_has_no_legs(bench, monkeypatch):
+    """Without --full every leg after the timed region is off, whatever its own option
+    says; --full leaves them as given."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2",
+                                      "--fallback-steps", "3"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu_baseline and a.no_idle_latency
+    assert a.fallback_steps == 0 and a.first_window_steps == 0
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not a.no_cpu_baseline and not a.no_idle_latency
+    assert a.fallback_steps == 3 and a.first_window_steps == 5
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--config", "3", "--dump-outputs", "x"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_files(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files of one step's results; wav and pcm16 whole when
+    they fit, else at the same seeded positions, identical from call to call."""
+    import numpy as np
+    import torch
+    from janus_amd.pipeline import EncodeResult
+    g = torch.Generator().manual_seed(3)
+    tokens = torch.randint(0, 51864, (4, 448), generator=g, dtype=torch.int32)
+    enc = EncodeResult(None, None, None, tokens, torch.tensor([447, 3, 10, 0], dtype=torch.int32),
+                       stats=torch.rand(4, 3, generator=g))
+    wav = torch.rand(4, 1000, generator=g) * 2 - 1
+    pcm16 = (wav * 32767).to(torch.int16)
+    bench.dump_outputs(str(tmp_path / "a"), enc, wav, pcm16)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == ["n_tokens", "pcm16", "stats", "tokens", "wav"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["tokens"], tokens.numpy()) and np.array_equal(got["wav"], wav.numpy())
+    assert np.array_equal(got["pcm16"], pcm16.numpy()) and got["n_tokens"].tolist() == [447, 3, 10, 0]
+    monkeypatch.setattr(bench, "DUMP_SAMPLES", 64)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), enc, wav, pcm16)
+    idx = np.load(tmp_path / "b" / "sample_index.npy")
+    assert idx.dtype == np.float64 and idx.shape == (64,) and np.all(np.diff(idx) >= 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "wav.npy"), wav.numpy().reshape(-1)[idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "b" / "pcm16.npy"), pcm16.numpy().reshape(-1)[idx.astype(np.int64)])
+    for f in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+
+
 def test_conv_avg_tool(tmp_path):
     """tools/conv_avg.py: encoder-stem convs and pack kernels excluded, the average of the
     rest compared with the line's HIP-event average."""

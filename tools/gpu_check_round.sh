@@ -19,13 +19,13 @@ f=$(find $out/prof -name "*.db" | head -1)
 python3 $root/tools/rocprof_stats.py "$f" 40 --csv $out/kernel_stats.csv > $out/kernel_top.txt
 grep '"metric"' $out/prof.log > $out/bench_under_rocprof.json
 cd $root
-timeout -k 10 600 python3 -u bench.py > $out/bench.log 2>&1 || { tail -20 $out/bench.log; exit 1; }
+timeout -k 10 600 python3 -u bench.py --full > $out/bench.log 2>&1 || { tail -20 $out/bench.log; exit 1; }
 tail -1 $out/bench.log > $out/bench.json
-timeout -k 10 300 python3 -u bench.py --config 2 --steps 5 --warmup 1 > $out/config2.log 2>&1 || { tail -20 $out/config2.log; exit 1; }
+timeout -k 10 300 python3 -u bench.py --config 2 --steps 5 --warmup 1 --full > $out/config2.log 2>&1 || { tail -20 $out/config2.log; exit 1; }
 tail -1 $out/config2.log > $out/config2.json
-timeout -k 10 300 python3 -u bench.py --config 3 --steps 5 --warmup 2 > $out/config3.log 2>&1 || { tail -20 $out/config3.log; exit 1; }
+timeout -k 10 300 python3 -u bench.py --config 3 --steps 5 --warmup 2 --full > $out/config3.log 2>&1 || { tail -20 $out/config3.log; exit 1; }
 tail -1 $out/config3.log > $out/config3.json
-timeout -k 10 300 python3 -u bench.py --config 1 --steps 5 --warmup 1 > $out/config1.log 2>&1 || { tail -20 $out/config1.log; exit 1; }
+timeout -k 10 300 python3 -u bench.py --config 1 --steps 5 --warmup 1 --full > $out/config1.log 2>&1 || { tail -20 $out/config1.log; exit 1; }
 tail -1 $out/config1.log > $out/config1.json
 timeout -k 10 300 python3 -u tools/stream_bench.py --model base.en > $out/stream5.log 2>&1 || { tail -20 $out/stream5.log; exit 1; }
 tail -1 $out/stream5.log > $out/stream5.json
