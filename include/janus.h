@@ -298,6 +298,11 @@ typedef struct {
 #define JANUS_DEC_PATH_XFWD         0x20000u /* persistent segments: every layer's one-split
                                                cross-attention over the key chunks first to
                                                last (default: odd layers last to first) */
+#define JANUS_DEC_PATH_XROWS(n)     ((((uint32_t)(n) >> 1) & 3u) << 18)
+                                            /* 12 heads, d_model 768: rows sharing an encoder
+                                               row read it in place in blocks of up to n = 2
+                                               or 4 rows (default: one gathered copy per row,
+                                               measured faster at 320 rows) */
 
 /*
  * Batched greedy decoding (temperature 0) with the Whisper logit rules
@@ -329,7 +334,10 @@ typedef struct {
    * transcriber.py:53-57 with the library's defaults): enc_index [host] int32 [B], row b
    * attends to encoder row enc_index[b] of enc, which then holds n_enc rows [n_enc][Te][d]
    * instead of B. The cross-attention reads each shared row once per PAIR of decoder rows
-   * (both rows' heads in one MFMA tile). NULL = row b attends to enc row b. */
+   * (both rows' heads in one MFMA tile) up to 8 heads / d_model 512; the 12-head models
+   * (d_model 768) gather one copy of its encoder row per decoder row unless
+   * JANUS_DEC_PATH_XROWS(n) asks for in-place blocks of n rows; janus_whisper_decode_path
+   * tells which of the two a call did. NULL = row b attends to enc row b. */
   const int32_t* enc_index;
   int n_enc;
   /* Staggered decode (continuous batching across calls): pos_offset [host] int32 [B], row b
@@ -400,6 +408,29 @@ int janus_whisper_decode_sample_rows_ex(janus_whisper* w, const uint16_t* enc, i
  * launches per position beside bytes per position); the reference has no counterpart.
  */
 int janus_whisper_decode_info(janus_whisper* w, int32_t* positions, int64_t* launches);
+
+/*
+ * Which path the last decode call on this context took (the lane janus_whisper_decode_info
+ * reports), read-only:
+ *   enc_rows    how the decoder rows reached their encoder output: JANUS_ENC_ROWS_OWN (no
+ *               enc_index: row b reads enc row b), JANUS_ENC_ROWS_IN_PLACE (enc_index: every
+ *               shared encoder row read in place, once per block of decoder rows — PAIR blocks
+ *               up to 8 heads; at 12 heads / d_model 768 blocks of two or four rows with
+ *               JANUS_DEC_PATH_XROWS(n)) or
+ *               JANUS_ENC_ROWS_GATHERED (enc_index: one copy of its encoder row per decoder
+ *               row, [Te][d] fp16 each — JANUS_DEC_PATH_NO_XPAIR / _NO_XABSORB, the 12-head
+ *               family's default, or a shape without a shared-row kernel)
+ *   persistent  the persistent level the call actually ran (0: the launch path; 1..3 as
+ *               janus_decode_options.persistent) — a shape the persistent segments do not
+ *               cover (any d_model but 512) silently keeps the launch path and reports 0.
+ * For the parity tests (a silent gather copy decodes the same tokens) and for serving code
+ * sizing its sampled batches; the reference has no counterpart (faster-whisper hides
+ * CTranslate2's batching, transcriber.py:53-57).
+ */
+#define JANUS_ENC_ROWS_OWN      0
+#define JANUS_ENC_ROWS_IN_PLACE 1
+#define JANUS_ENC_ROWS_GATHERED 2
+int janus_whisper_decode_path(janus_whisper* w, int32_t* enc_rows, int32_t* persistent);
 
 /*
  * Where each of the `batch` row slots stands after the last completed decode call (the

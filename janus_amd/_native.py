@@ -81,6 +81,7 @@ SIGNATURES = {
     "janus_whisper_decode_sample_rows_ex": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "janus_whisper_decode_check": [_P, _I32],
     "janus_whisper_decode_info": [_P, _P, _P],
+    "janus_whisper_decode_path": [_P, _P, _P],
     "janus_whisper_decode_stand": [_P, _P, _I32],
     "janus_whisper_decode_stand_slot": [_P, _I32, _P, _I32],
     "janus_vocoder_create": [_P, _P],

@@ -626,6 +626,7 @@ __global__ __launch_bounds__(512) void decode_combine_reg_kernel(const float* __
 constexpr int kHeadWaves = 8;
 constexpr int kHeadRounds = 8;                               // key groups per wave
 constexpr int kHeadKeys = 8 * kHeadWaves * kHeadRounds;      // 512
+constexpr int kHeadMaxHeads = 16;                            // grid.x; no per-head storage
 
 // NR: key rounds actually holding keys (ceil(Tkv / 64)): the rounds past the cache end
 // only loaded the clamped last row and added p = 0 — dropping them changes no bit.
@@ -750,7 +751,9 @@ void decode_attention_split_launch(const _Float16* q, int64_t q_bs, const _Float
                                    _Float16* out, int64_t o_bs, int B, int H, float scale,
                                    float* part_o, float* part_ml, hipStream_t s,
                                    const int32_t* roff, int max_roff) {
-  JANUS_CHECK(H <= kMaxHeads, "split decode attention: at most 8 heads (d <= 512)");
+  // the per-head kernel (grid H x B) sizes nothing by H; the split-key kernels below hold
+  // kMaxHeads heads per block in LDS and 8-dim slices of one key row in 64 lanes
+  JANUS_CHECK(H >= 1 && H <= kHeadMaxHeads, "decode attention: at most 16 heads (d <= 1024)");
   if (B <= 0 || Tkv <= 0) return;
   static const bool force_split = ab_env("JANUS_DEC_SPLIT") != nullptr;
   const int tmax = Tkv + (roff ? max_roff : 0);
@@ -773,6 +776,9 @@ void decode_attention_split_launch(const _Float16* q, int64_t q_bs, const _Float
     JANUS_LAUNCH_CHECK();
     return;
   }
+  JANUS_CHECK(H <= kMaxHeads, "split decode attention (more than 512 keys): at most 8 heads (d <= 512)");
+  static_assert(kMaxHeads * 8 <= 64 && kMaxHeads * kHd <= 512,
+                "split kernels: one 8-dim slice per lane of a wave, combine blocks of H * 64 <= 512 threads");
   const int nsplit = decode_split_count(Tkv);
   const int chunk = (Tkv + nsplit - 1) / nsplit;
   JANUS_CHECK(chunk <= kSplitKeys && nsplit <= 64, "split decode attention: too many keys");

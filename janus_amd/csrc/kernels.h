@@ -132,6 +132,17 @@ void xattn_launch(const _Float16* qk, const _Float16* enc, int B, int Te, int D,
 void xattn_group_launch(const _Float16* qk, const _Float16* enc, int Te, int D, int H, int nsplit,
                         float* part_c, float* part_ml, hipStream_t s, const int* groups, int ngroups,
                         int rows_per_group);
+// The 12-head family (D = 768): blocks of <= xattn_rows_max(D, H) = 4 decoder rows sharing an
+// encoder row, 12 heads per row packed into 1..3 MFMA m-tiles; groups as above (row_4, row_5
+// unused). Writes the partials the one-row xattn_launch(combine = false) writes, bit for
+// bit; xattn_combine_launch merges them as xattn_launch(combine = true) does.
+bool xattn_rows_supported(int D, int H);
+int xattn_rows_max(int D, int H);
+void xattn_rows_launch(const _Float16* qk, const _Float16* enc, int Te, int D, int H, int nsplit,
+                       float* part_c, float* part_ml, hipStream_t s, const int* groups, int ngroups,
+                       int rows_per_group);
+void xattn_combine_launch(const float* part_c, const float* part_ml, int nsplit, int B, int H, int D,
+                          _Float16* out, hipStream_t s);
 // The split merge of xattn_launch(..., combine = false) fused with the per-head value
 // projection: out[b][64h + j] = merge_s(part)[b][h] . wv[64h + j]^T + bv[64h + j]
 // (wv [H*64][D] fp16, out row stride ldo); bit-identical to the merge kernel followed by the

@@ -70,6 +70,9 @@ struct DecLane {
   std::vector<float> h_itemp;    // per-row 1 / T of the last call (source of an async copy)
   std::map<std::vector<int64_t>, hipGraphExec_t> graphs;
   std::map<std::vector<int64_t>, size_t> graph_nodes;  // kernel nodes per captured graph
+  // the path the last decode call took (janus_whisper_decode_path): how its rows reached
+  // their encoder output (JANUS_ENC_ROWS_*) and the persistent level it ran (0: launches)
+  int last_enc_rows = 0, last_persist = 0;
   int last_positions = 0;        // positions the last decode stepped
   int64_t last_launches = 0;     // kernel launches those positions issued (graph nodes)
   // where each row slot stands after the last call (positions whose KV rows and next
@@ -348,8 +351,18 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
     for (int b = 0; b < B; ++b)
       JANUS_CHECK(rows->enc_index[b] >= 0 && rows->enc_index[b] < n_enc, "decode: enc_index out of range");
   }
-  const bool pair_ok = shared && xattn_supported(d, H) && H <= 8 && d <= 512 && B <= kSkinnyMaxRows &&
-                       !path(JANUS_DEC_PATH_NO_XABSORB) && !path(JANUS_DEC_PATH_NO_XPAIR);
+  // (H <= 8, d <= 512: PAIR blocks, the default there. The 12-head family at d = 768 —
+  // `wide` — has blocks of up to two or four rows, xattn_rows_kernel, behind
+  // JANUS_DEC_PATH_XROWS(n): measured SLOWER than the gathered copies at 320 rows, DESIGN.md
+  // §5i, so without the flag its shared rows are gathered)
+  const bool wide = !(H <= 8 && d <= 512);
+  const int xrows = 2 * (int)((pf >> 18) & 3u);   // JANUS_DEC_PATH_XROWS(n): n = 2 or 4, 0 = off
+  JANUS_CHECK(xrows == 0 || (xattn_rows_supported(d, H) && xrows <= xattn_rows_max(d, H)),
+              "decode: JANUS_DEC_PATH_XROWS(n) is n = 2 or 4 rows per block at 12 heads, d_model 768");
+  const bool pair_ok = shared && xattn_supported(d, H) && (!wide || xrows > 0) &&
+                       B <= kSkinnyMaxRows && !path(JANUS_DEC_PATH_NO_XABSORB) && !path(JANUS_DEC_PATH_NO_XPAIR);
+  JANUS_CHECK(!(wide && path(JANUS_DEC_PATH_XGROUP)),
+              "decode: JANUS_DEC_PATH_XGROUP (GROUP blocks of 8-head rows) needs H <= 8, d <= 512");
   // rows sharing an encoder row (best_of = 5 hypotheses of a window): PAIR blocks
   // (xattn_kernel<PAIR>, two blocks per CU, the window's output read once per two rows).
   // GROUP blocks of up to 6 rows (xattn_group_kernel: one read for all hypotheses) are
@@ -357,13 +370,32 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
   // step, two same-box pairs, profiles/r04_lanes_sweep_fallback_ab.json) — one block per
   // CU with three m-tiles of queries staged through LDS loses more than the reads it saves
   std::vector<int> h_groups;
-  int grp_rows = 0;
+  int grp_rows = 0, rem_rows = 0, n_main = -1;   // (wide: groups [n_main, ngroups) hold <= rem_rows rows)
   if (pair_ok) {
     std::vector<std::vector<int>> grp(n_enc);
     for (int b = 0; b < B; ++b) grp[rows->enc_index[b]].push_back(b);
     size_t maxg = 0;
     for (auto& g : grp) maxg = std::max(maxg, g.size());
-    if (maxg > 2 && path(JANUS_DEC_PATH_XGROUP)) {
+    if (wide) {
+      // blocks of up to xrows rows of one encoder row, in row order (4: best_of = 5 is 4 + 1)
+      grp_rows = (int)std::min<size_t>((size_t)xrows, maxg);
+      // each encoder row's remainder rows (fewer than a full block) go out as blocks of a
+      // second launch with their own, smaller m-tile count (a lone row: one m-tile, two blocks
+      // per CU): 5 493 -> 4 496 us per position at 320 rows on small.en, DESIGN.md §5i;
+      // JANUS_XROWS_ONE_LAUNCH (A/B builds) keeps them in the full blocks' launch
+      static const bool split_rem = ab_env("JANUS_XROWS_ONE_LAUNCH") == nullptr;
+      std::vector<int> rem;
+      for (int e = 0; e < n_enc; ++e)
+        for (size_t i = 0; i < grp[e].size(); i += grp_rows) {
+          const size_t n = std::min<size_t>(grp_rows, grp[e].size() - i);
+          std::vector<int>& dst = (split_rem && (int)n < grp_rows) ? rem : h_groups;
+          if (&dst == &rem) rem_rows = std::max(rem_rows, (int)n);
+          dst.push_back(e);
+          for (int j = 0; j < 7; ++j) dst.push_back(j < (int)n ? grp[e][i + j] : -1);
+        }
+      n_main = (int)h_groups.size() / 8;
+      h_groups.insert(h_groups.end(), rem.begin(), rem.end());
+    } else if (maxg > 2 && path(JANUS_DEC_PATH_XGROUP)) {
       grp_rows = (int)std::min<size_t>(6, maxg);
       for (int e = 0; e < n_enc; ++e)
         for (size_t i = 0; i < grp[e].size(); i += grp_rows) {
@@ -821,8 +853,16 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
         }
         // o_h = c_h Wv_h^T + bv_h (block-diagonal over heads), then x += o Wo^T + bo; the
         // split merge and the value projection in one launch (cvp) where supported
-        JANUS_CHECK(!xgroups || cvp, "decode: shared-encoder groups need the fused merge (no JANUS_DEC_PATH_NO_CVP)");
-        if (xgroups)
+        JANUS_CHECK(!xgroups || cvp || wide, "decode: shared-encoder groups need the fused merge (no JANUS_DEC_PATH_NO_CVP)");
+        if (xgroups && wide) {
+          const int nm = n_main >= 0 ? n_main : ngroups;
+          xattn_rows_launch(xqk, enc, Te, d, H, xsplit, Z.d_xpc.as<float>(), Z.d_xpml.as<float>(), s,
+                            xgroups, nm, grp_rows);
+          if (ngroups > nm)
+            xattn_rows_launch(xqk, enc, Te, d, H, xsplit, Z.d_xpc.as<float>(), Z.d_xpml.as<float>(), s,
+                              xgroups + 8 * nm, ngroups - nm, rem_rows);
+          if (!cvp) xattn_combine_launch(Z.d_xpc.as<float>(), Z.d_xpml.as<float>(), xsplit, B, H, d, xc, s);
+        } else if (xgroups)
           xattn_group_launch(xqk, enc, Te, d, H, xsplit, Z.d_xpc.as<float>(), Z.d_xpml.as<float>(), s,
                              xgroups, ngroups, grp_rows);
         else
@@ -895,7 +935,7 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
       R.no_timestamps, R.max_initial_ts, R.target, (int64_t)Z.d_prompt.p, (int64_t)Z.d_nsp.p,
       (int64_t)sampling, (int64_t)float_bits(R.inv_temp), (int64_t)Z.d_seed.p, (int64_t)row_temps,
       (int64_t)Z.d_itemp.p, (int64_t)xpairs,
-      (int64_t)npairs, (int64_t)xgroups, (int64_t)ngroups, (int64_t)grp_rows, (int64_t)roff,
+      (int64_t)npairs, (int64_t)xgroups, (int64_t)ngroups, (int64_t)grp_rows, (int64_t)n_main, (int64_t)rem_rows, (int64_t)roff,
       (int64_t)max_roff, (int64_t)persist + (int64_t)layerk + (int64_t)xfuse, (int64_t)seg_grid, (int64_t)Z.d_omid.p, (int64_t)Z.d_segbar.p,
       (int64_t)Z.d_segerr.p};
   arrival.now();  // all lanes' allocations done: captures may start
@@ -906,6 +946,8 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
   }
   Z.last_positions = 0;
   Z.last_launches = 0;
+  Z.last_enc_rows = !shared ? JANUS_ENC_ROWS_OWN : pair_ok ? JANUS_ENC_ROWS_IN_PLACE : JANUS_ENC_ROWS_GATHERED;
+  Z.last_persist = (int)persist + (int)layerk + (int)xfuse;
   for (int p0 = 0; p0 < steps; p0 += chunk) {
     const int n = std::min(chunk, steps - p0);
     Z.last_positions += n;
@@ -1146,6 +1188,16 @@ extern "C" int janus_whisper_decode_info(janus_whisper* w, int32_t* positions, i
     const int sl = w->last_slot < (int)w->lanes.size() ? w->last_slot : 0;
     *positions = w->lanes.empty() ? 0 : w->lanes[sl]->last_positions;
     *launches = w->lanes.empty() ? 0 : w->lanes[sl]->last_launches;
+  });
+}
+
+extern "C" int janus_whisper_decode_path(janus_whisper* w, int32_t* enc_rows, int32_t* persistent) {
+  return guarded([&] {
+    JANUS_CHECK(w && enc_rows && persistent, "null argument");
+    std::lock_guard<std::mutex> lk(w->mu);
+    const int sl = w->last_slot < (int)w->lanes.size() ? w->last_slot : 0;
+    *enc_rows = w->lanes.empty() ? JANUS_ENC_ROWS_OWN : w->lanes[sl]->last_enc_rows;
+    *persistent = w->lanes.empty() ? 0 : w->lanes[sl]->last_persist;
   });
 }
 

@@ -53,7 +53,7 @@ import torch
 from .. import _native as nat
 from ..common import wavio
 from ..tokenizer import SOT_PREV
-from ..whisper import CONFIGS, WhisperEngine
+from ..whisper import CONFIGS, WhisperEngine, shared_rows_in_place
 
 WINDOW_16K = 480000
 N_FRAMES = 3000          # log-mel frames per window (hop 160 @ 16 kHz)
@@ -69,7 +69,17 @@ PROMPT_RESET_ON_TEMPERATURE = 0.5
 FALLBACK_ROWS = 320      # hypotheses per sampling decode (64 windows x 5: one decode per
                          # temperature for a 64-window round; the windows' encoder outputs are
                          # shared by their hypotheses through enc_index)
-FALLBACK_ROWS_GATHER = 60  # the same for models past the PAIR path's H <= 8, d <= 512
+FALLBACK_ROWS_GATHER = 60  # the same for models without a shared-row cross-attention kernel
+                           # (whisper.shared_rows_in_place): one encoder copy per row
+
+
+def fallback_rows(engine) -> int:
+    """Rows of one sampled decode call on this engine's model: FALLBACK_ROWS where rows
+    sharing an encoder row read it in place (tiny.en / base.en PAIR blocks),
+    FALLBACK_ROWS_GATHER where every row gets its own encoder copy (the 768-wide 12-head
+    family by measurement, DESIGN.md §5i, and any wider model). An engine without a ``cfg``
+    (a test stub) counts as in place."""
+    return FALLBACK_ROWS if shared_rows_in_place(getattr(engine, "cfg", None)) else FALLBACK_ROWS_GATHER
 
 
 def _mix32(h: int) -> int:
@@ -279,9 +289,7 @@ def _fallback(engine, tk, enc, prompts, first, keys, max_length, temperatures, b
     # the shared-encoder PAIR path (H <= 8, d <= 512) reads each window's output in place;
     # wider models gather one encoder copy per hypothesis row (0.74 GB per 320 rows at
     # d = 768), so their sampled decodes stay at FALLBACK_ROWS_GATHER rows
-    cfg = getattr(engine, "cfg", None)
-    pair = cfg is None or (cfg.n_heads <= 8 and cfg.d_model <= 512)
-    per = max(1, (FALLBACK_ROWS if pair else FALLBACK_ROWS_GATHER) // best_of)
+    per = max(1, fallback_rows(engine) // best_of)
     for ti in range(1, len(temperatures)):
         T = float(temperatures[ti])
         pend = [j for j in range(len(first)) if final[j] is None]
@@ -420,7 +428,8 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     spec = speculative and len(temperatures) > 1
     per_row = 1 + (len(temperatures) - 1) * best_of          # rows per window, speculative
     if spec:
-        max_batch = max(1, min(max_batch, FALLBACK_ROWS // per_row))
+        # the same in-place-or-gather row cap as the sequential fallback (_fallback)
+        max_batch = max(1, min(max_batch, fallback_rows(engine) // per_row))
     while True:
         act = [i for i, s in enumerate(streams) if s.active]
         if not act:

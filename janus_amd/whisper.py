@@ -41,6 +41,8 @@ CONFIGS = {
     "tiny.en": WhisperConfig("tiny.en", 384, 6, 4, 4),
     "base.en": WhisperConfig("base.en", 512, 8, 6, 6),
     "small.en": WhisperConfig("small.en", 768, 12, 12, 12),
+    # distil-whisper: small.en's encoder over a 4-layer decoder
+    "distil-small.en": WhisperConfig("distil-small.en", 768, 12, 12, 4),
 }
 
 
@@ -78,6 +80,12 @@ DEC_PATH_NO_EMBED_LN = 0x0400
 DEC_PATH_LN_PROLOGUE = 0x0800
 DEC_PATH_SEG_2CU = 0x10000
 DEC_PATH_XFWD = 0x20000
+
+
+def dec_path_xrows(n: int) -> int:
+    """JANUS_DEC_PATH_XROWS(n): 12 heads / d_model 768, rows sharing an encoder row read it
+    in place in blocks of up to n = 2 or 4 rows (default there: a gathered copy per row)."""
+    return ((n >> 1) & 3) << 18
 
 
 def dec_path_ln_mask(m: int) -> int:
@@ -234,8 +242,23 @@ def load_weights(cfg: WhisperConfig, seed: int = 0) -> dict:
         if emb is None or emb.shape != (cfg.n_vocab, cfg.d_model):
             raise ValueError(f"checkpoint does not match {cfg.name}: decoder.embed_tokens.weight "
                              f"{None if emb is None else emb.shape}")
+        # depth per side: a distil checkpoint keeps the teacher's encoder (12 layers at
+        # small.en's width) over a 4-layer decoder, so the two counts are checked apart
+        for side, want in (("encoder", cfg.enc_layers), ("decoder", cfg.dec_layers)):
+            have = checkpoint_layers(W, side)
+            if have != want:
+                raise ValueError(f"checkpoint does not match {cfg.name}: {have} {side} layers, "
+                                 f"the config has {want}")
         return engine_weights(W)
     return synthetic_weights(cfg, seed)
+
+
+def checkpoint_layers(W: dict, side: str) -> int:
+    """Layers a checkpoint holds on one side ("encoder" / "decoder"): 1 + the largest index
+    among its ``<side>.layers.<i>.`` tensor names (0 when it has none)."""
+    pre = side + ".layers."
+    idx = [int(k[len(pre):].split(".", 1)[0]) for k in W if k.startswith(pre)]
+    return max(idx) + 1 if idx else 0
 
 
 # --------------------------------------------------------------------- engine
@@ -456,12 +479,42 @@ class WhisperEngine:
         nat.call("janus_whisper_decode_info", self._h, ctypes.addressof(pos), ctypes.addressof(lau))
         return int(pos.value), int(lau.value)
 
+    def decode_path(self):
+        """Which path the last decode call took (janus_whisper_decode_path): a DecodePath
+        of ``enc_rows`` ("own": no enc_index; "in_place": shared encoder rows read where
+        they lie; "gathered": one encoder copy per decoder row) and ``persistent`` (the
+        persistent level actually run; 0 = the launch path)."""
+        er, ps = ctypes.c_int32(0), ctypes.c_int32(0)
+        nat.call("janus_whisper_decode_path", self._h, ctypes.addressof(er), ctypes.addressof(ps))
+        return DecodePath(ENC_ROWS_NAMES[int(er.value)], int(ps.value))
+
     def texts(self, tokens: torch.Tensor, prompt_lens=None):
         """Host-side detokenisation of decoded rows (after each row's prompt)."""
         t = tokens.cpu().numpy()
         plen = len(self.tokenizer.sot_sequence)
         pl = prompt_lens if prompt_lens is not None else [plen] * len(t)
         return [self.tokenizer.transcript(row[int(p):]) for row, p in zip(t, pl)]
+
+
+# janus_whisper_decode_path enc_rows (include/janus.h JANUS_ENC_ROWS_*)
+ENC_ROWS_NAMES = ("own", "in_place", "gathered")
+
+
+@dataclasses.dataclass(frozen=True)
+class DecodePath:
+    enc_rows: str      # "own" | "in_place" | "gathered"
+    persistent: int    # persistent level the call ran (0: the launch path)
+
+
+def shared_rows_in_place(cfg) -> bool:
+    """True when decoder rows sharing an encoder row (enc_index) read it in place by default
+    on this model: PAIR blocks up to 8 heads / d_model 512 (whisper.cpp pair_ok). Otherwise a
+    call gathers one encoder copy per row — the 768-wide 12-head family too, whose in-place
+    blocks (DEC_PATH_XROWS) measured slower than the copies — and callers keep their
+    sampled batches small (services/transcriber.py FALLBACK_ROWS_GATHER)."""
+    if cfg is None:
+        return True
+    return cfg.n_heads <= 8 and cfg.d_model <= 512
 
 
 @dataclasses.dataclass
