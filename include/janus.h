@@ -221,6 +221,19 @@ int janus_whisper_logmel_frames(janus_whisper* w, const float* pcm, const int64_
 /* Encoder forward: mel [device] fp16 [B][3000][80] -> enc [device] fp16 [B][1500][d]. */
 int janus_whisper_encode(janus_whisper* w, const uint16_t* mel, int batch, uint16_t* enc,
                          void* stream);
+/*
+ * Compute type of the encoder's linear layers (fused QKV, out_proj, fc1, fc2 of every
+ * encoder layer). F16 (the default): fp16 weights and activations on the fp16 MFMA. INT8:
+ * CTranslate2's int8 compute type (transcriber.py:23-27, compute_type='int8') — weights
+ * quantised per output row from the fp32 parameters on first use (and again after a
+ * janus_whisper_set_tensor), activations per row on the fly, int32 accumulation on the i8
+ * MFMA. The conv stem, attention, LayerNorms, residual stream and the whole decoder are the
+ * same in both modes. The mode may be switched between calls, in either direction.
+ */
+#define JANUS_ENC_COMPUTE_F16 0
+#define JANUS_ENC_COMPUTE_INT8 1
+int janus_whisper_set_encoder_compute(janus_whisper* w, int mode);
+int janus_whisper_encoder_compute(janus_whisper* w, int32_t* mode);
 
 typedef struct {
   const int32_t* prompt;   /* [host] initial tokens, e.g. {<|startoftranscript|>} for *.en */

@@ -58,6 +58,38 @@ int janus_gemm_ln_f16(int epi, const float* x, int64_t ldx, const float* gamma, 
 int janus_layernorm_f16(const float* x, const float* gamma, const float* beta, uint16_t* out,
                         int rows, int d, float eps, void* stream);
 
+/*
+ * Int8 projections (gemm_i8.hip): the encoder's linear layers under
+ * janus_whisper_set_encoder_compute(JANUS_ENC_COMPUTE_INT8), CTranslate2's int8 compute type
+ * (transcriber.py:23-27, compute_type='int8').
+ *
+ * Row-wise symmetric quantiser, per row x[0..K): amax = max |x[k]| (exact in fp32);
+ * amax == 0: q = 0, scale = 1.0f; otherwise inv = 127.0f / amax (correctly rounded),
+ * q[k] = (int8) clamp(rintf(x[k] * inv), -127, 127) (one rounding in the product, ties of
+ * rintf to even), scale = amax / 127.0f (correctly rounded).
+ * x fp16 [M][K] with row stride ldx -> q int8 [M][K] with row stride ldq, scale f32 [M].
+ * K % 16 == 0, K <= 3072, any M.
+ */
+int janus_quant_rows_i8(const uint16_t* x, int64_t ldx, int8_t* q, int64_t ldq, float* scale, int M,
+                        int K, void* stream);
+/* janus_layernorm_f16 followed by janus_quant_rows_i8 in one pass over x f32 [rows][d], bit
+ * for bit (q int8 [rows][d], scale f32 [rows]); the fp16 row is never written. d % 16 == 0,
+ * d <= 2048. */
+int janus_layernorm_quant_i8(const float* x, const float* gamma, const float* beta, int8_t* q,
+                             float* scale, int rows, int d, float eps, void* stream);
+/*
+ * C[M,N] = epi( float(sum_k A[m,k] * W[n,k]) * (a_scale[m] * w_scale[n]) + bias[n] ):
+ * int8 A [M][K] and W [N][K] (K contiguous), exact int32 accumulation on
+ * v_mfma_i32_16x16x64_i8, then in fp32 with one rounding per operation (no fma):
+ * s = a_scale[m] * w_scale[n]; y = (float)acc * s + bias[n] (bias may be NULL: 0).
+ * epi JANUS_EPI_F32: y; JANUS_EPI_F16: fp16(y); JANUS_EPI_GELU_F16: fp16(gelu(y));
+ * JANUS_EPI_RESID_F32: C = R + y (R may alias C). Any M; N % 128 == 0 and K % 128 == 0
+ * (an error otherwise); lda, ldw multiples of 16, ldc of 8; 16-byte aligned operands.
+ */
+int janus_gemm_i8(int epi, const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,
+                  const float* a_scale, const float* w_scale, const float* bias, void* C, int64_t ldc,
+                  const float* R, int64_t ldr, int M, int N, int K, void* stream);
+
 /* The cross-lane moves every wave reduction of the library uses (DPP / v_permlane swaps in
  * place of ds_bpermute): in [device] f32 [n_waves][64] -> out [device] f32 [n_waves][6][64],
  * out[w][k][l] = in[w][l ^ (1 << k)] when they are right. Test entry. */

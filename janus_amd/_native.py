@@ -75,6 +75,8 @@ SIGNATURES = {
     "janus_whisper_logmel": [_P, _P, _P, _I32, _I32, _P, _P, _P],
     "janus_whisper_logmel_frames": [_P, _P, _P, _I32, _I32, _I32, _P, _P],
     "janus_whisper_encode": [_P, _P, _I32, _P, _P],
+    "janus_whisper_set_encoder_compute": [_P, _I32],
+    "janus_whisper_encoder_compute": [_P, _P],
     "janus_whisper_decode_greedy": [_P, _P, _I32, _P, _P, _P, _P, _P],
     "janus_whisper_decode_greedy_ex": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
     "janus_whisper_decode_sample_ex": [_P, _P, _I32, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P],
@@ -101,6 +103,9 @@ SIGNATURES = {
     "janus_gemm_lt_f16": [_I32, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _P],
     "janus_layernorm_f16": [_P, _P, _P, _P, _I32, _I32, _F32, _P],
     "janus_wave_xor_f32": [_P, _P, _I32, _P],
+    "janus_quant_rows_i8": [_P, _I64, _P, _I64, _P, _I32, _I32, _P],
+    "janus_layernorm_quant_i8": [_P, _P, _P, _P, _P, _I32, _I32, _F32, _P],
+    "janus_gemm_i8": [_I32, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _P],
     "janus_resid_ln_f16": [_P, _I64, _P, _I64, _P, _P, _P, _P, _F32, _P, _I32, _I32, _I32, _P],
     "janus_gemm_ln_f16": [_I32, _P, _I64, _P, _P, _F32, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _P],
     "janus_attention_f16": [_P, _P, _I32, _I32, _I32, _F32, _P],

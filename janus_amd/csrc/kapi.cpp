@@ -111,6 +111,36 @@ extern "C" int janus_layernorm_f16(const float* x, const float* gamma, const flo
   });
 }
 
+extern "C" int janus_quant_rows_i8(const uint16_t* x, int64_t ldx, int8_t* q, int64_t ldq, float* scale,
+                                   int M, int K, void* stream) {
+  return guarded([&] {
+    quant_rows_i8_launch(reinterpret_cast<const _Float16*>(x), ldx, q, ldq, scale, M, K,
+                         (hipStream_t)stream);
+  });
+}
+
+extern "C" int janus_layernorm_quant_i8(const float* x, const float* gamma, const float* beta,
+                                        int8_t* q, float* scale, int rows, int d, float eps,
+                                        void* stream) {
+  return guarded([&] {
+    layernorm_quant_i8_launch(x, gamma, beta, q, scale, rows, d, eps, (hipStream_t)stream);
+  });
+}
+
+extern "C" int janus_gemm_i8(int epi, const int8_t* A, int64_t lda, const int8_t* W, int64_t ldw,
+                             const float* a_scale, const float* w_scale, const float* bias, void* C,
+                             int64_t ldc, const float* R, int64_t ldr, int M, int N, int K,
+                             void* stream) {
+  return guarded([&] {
+    GemmI8Args g;
+    g.A = reinterpret_cast<const signed char*>(A); g.lda = lda;
+    g.W = reinterpret_cast<const signed char*>(W); g.ldw = ldw;
+    g.a_scale = a_scale; g.w_scale = w_scale; g.bias = bias; g.C = C; g.ldc = ldc;
+    g.R = R; g.ldr = ldr; g.M = M; g.N = N; g.K = K;
+    gemm_i8_launch(epi, g, (hipStream_t)stream);
+  });
+}
+
 extern "C" int janus_wave_xor_f32(const float* in, float* out, int n_waves, void* stream) {
   return guarded([&] {
     JANUS_CHECK(in && out, "null argument");

@@ -86,6 +86,35 @@ struct SkinnyLnArgs {
 };
 void gemm_skinny_ln_launch(int epi, const SkinnyLnArgs& p, hipStream_t s);
 
+// ------------------------------------------------- int8 projections (gemm_i8.hip)
+// Row-wise symmetric quantiser (CTranslate2's rule): per row amax = max |x|; amax == 0:
+// q = 0, scale = 1; else q = clamp(rint(x * (127 / amax)), -127, 127), scale = amax / 127.
+// x [M][K] (row stride ldx) -> q int8 [M][K] (row stride ldq), scale [M]. K % 16 == 0,
+// K <= 3072, any M. fp16 rows (activations) or fp32 rows (weights).
+void quant_rows_i8_launch(const _Float16* x, int64_t ldx, int8_t* q, int64_t ldq, float* scale, int M,
+                          int K, hipStream_t s);
+void quant_rows_f32_i8_launch(const float* x, int64_t ldx, int8_t* q, int64_t ldq, float* scale, int M,
+                              int K, hipStream_t s);
+// layernorm_launch followed by quant_rows_i8_launch in one pass, bit for bit; the fp16 row
+// is never written. d % 16 == 0, d <= 2048.
+void layernorm_quant_i8_launch(const float* x, const float* g, const float* b, int8_t* q, float* scale,
+                               int rows, int d, float eps, hipStream_t s);
+// C[M,N] = epi( float(sum_k A[m,k] W[n,k]) * (a_scale[m] * w_scale[n]) + bias[n] ), int32
+// accumulation on v_mfma_i32_16x16x64_i8; every fp32 operation rounded once (no fma).
+// epi: EPI_F16 | EPI_GELU_F16 | EPI_RESID_F32 (C = R + y, R may alias C) | EPI_F32.
+// Any M; N % 128 == 0 and K % 128 == 0 (every encoder projection of the four CONFIGS).
+struct GemmI8Args {
+  const signed char* A; int64_t lda;   // [M][K]
+  const signed char* W; int64_t ldw;   // [N][K]
+  const float* a_scale;                // [M]
+  const float* w_scale;                // [N]
+  const float* bias;                   // [N] or null
+  void* C; int64_t ldc;                // fp16 or fp32 by epilogue
+  const float* R; int64_t ldr;         // fp32 residual (EPI_RESID_F32)
+  int M, N, K;
+};
+void gemm_i8_launch(int epi, const GemmI8Args& p, hipStream_t s);
+
 // ------------------------------------------------------------- LayerNorm
 // out[r][:] = fp16( (x[r]-mean)/sqrt(var+eps) * g + b ), x fp32 [rows][d]
 // out[w][k][lane] = mfma.h xshfl<2^k>(in[w][lane]) (kernel test entry)

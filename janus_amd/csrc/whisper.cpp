@@ -24,6 +24,9 @@ namespace janus {
 
 struct EncLayer {
   DevMem wqkv, bqkv, wo, w1, w2;  // fp16 weights / fp32 fused bias
+  // int8 copies of the same four weights, quantised per output row from the fp32 parameters,
+  // and their dequantisation scales (prepare_i8: made when the int8 encoder is first used)
+  DevMem qqkv, sqkv, qo, so, q1, s1, q2, s2;
   const float *bo, *b1, *b2, *ln1g, *ln1b, *ln2g, *ln2b;
 };
 struct DecLayer {
@@ -108,6 +111,8 @@ struct janus_whisper {
   janus_whisper_config cfg;
   janus::ParamStore params;
   bool prepared = false;
+  int enc_compute = JANUS_ENC_COMPUTE_F16;  // janus_whisper_set_encoder_compute
+  bool i8_prepared = false;                 // the encoder layers hold their int8 weights
   std::mutex mu;
   // device-side prepared weights
   janus::DevMem conv1p, conv2p, pos16, tok16;
@@ -115,6 +120,7 @@ struct janus_whisper {
   std::vector<janus::DecLayer> dec;
   // workspaces
   janus::DevMem ws_x1, ws_x2, ws_r, ws_a, ws_qkv, ws_o, ws_f, ws_logmel, ws_maxkey;
+  janus::DevMem ws_q8, ws_qs;  // int8 encoder: quantised GEMM input rows and their scales
   // decoder lanes: each owns the workspaces, captured graphs and stream of one batch slice
   std::vector<std::unique_ptr<janus::DecLane>> lanes;
   int last_slot = 0;  // state slot of the last decode call (decode_info reports it)
@@ -183,6 +189,7 @@ static void prepare(janus_whisper* w, hipStream_t s) {
   const int64_t dd = (int64_t)d * d, fd = (int64_t)ff * d;
   w->enc.clear();
   w->enc.resize(c.enc_layers);
+  w->i8_prepared = false;  // the int8 copies went with the layers
   for (int l = 0; l < c.enc_layers; ++l) {
     const std::string p = "encoder.layers." + std::to_string(l) + ".";
     EncLayer& L = w->enc[l];
@@ -238,6 +245,39 @@ static void prepare(janus_whisper* w, hipStream_t s) {
   w->prepared = true;
 }
 
+// The int8 copies of the encoder's linear weights: each output row of the fp32 parameter
+// quantised on its own (the fused QKV weight row by row of its three parts).
+static void prepare_i8(janus_whisper* w, hipStream_t s) {
+  if (w->i8_prepared) return;
+  const auto& c = w->cfg;
+  const int d = c.d_model, ff = 4 * d;
+  const ParamStore& P = w->params;
+  auto quant = [&](const std::string& name, int rows, int cols, int8_t* q, float* sc) {
+    if (P.has(name)) {
+      quant_rows_f32_i8_launch(P.get(name, (int64_t)rows * cols), cols, q, cols, sc, rows, cols, s);
+    } else {  // as fuse_f16: a missing part is zeros (scale 0: the product is 0 either way)
+      JANUS_HIP(hipMemsetAsync(q, 0, (size_t)rows * cols, s));
+      JANUS_HIP(hipMemsetAsync(sc, 0, sizeof(float) * rows, s));
+    }
+  };
+  for (int l = 0; l < c.enc_layers; ++l) {
+    const std::string p = "encoder.layers." + std::to_string(l) + ".";
+    EncLayer& L = w->enc[l];
+    L.qqkv.ensure((size_t)3 * d * d); L.sqkv.ensure(sizeof(float) * 3 * d);
+    L.qo.ensure((size_t)d * d);       L.so.ensure(sizeof(float) * d);
+    L.q1.ensure((size_t)ff * d);      L.s1.ensure(sizeof(float) * ff);
+    L.q2.ensure((size_t)d * ff);      L.s2.ensure(sizeof(float) * d);
+    const char* part[3] = {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight"};
+    for (int i = 0; i < 3; ++i)
+      quant(p + part[i], d, d, L.qqkv.as<int8_t>() + (int64_t)i * d * d, L.sqkv.as<float>() + i * d);
+    quant(p + "self_attn.out_proj.weight", d, d, L.qo.as<int8_t>(), L.so.as<float>());
+    quant(p + "fc1.weight", ff, d, L.q1.as<int8_t>(), L.s1.as<float>());
+    quant(p + "fc2.weight", d, ff, L.q2.as<int8_t>(), L.s2.as<float>());
+  }
+  JANUS_HIP(hipStreamSynchronize(s));
+  w->i8_prepared = true;
+}
+
 // The encoder's projections (M = B * 1500 rows): gemm_launch dispatches them to the
 // 256 x 256-tile LDS-DMA kernel (gemm_big.hip) when N % 256 == 0 (base.en: every one).
 static void enc_gemm(int epi, const GemmArgs& g, hipStream_t s) { gemm_launch(epi, g, s); }
@@ -286,6 +326,38 @@ static void encode(janus_whisper* w, const _Float16* mel, int B, _Float16* out, 
   cast_f16_f32_launch(x2, r, M * d, s);
 
   const float scale = 0.125f;  // head_dim 64 ** -0.5
+  if (w->enc_compute == JANUS_ENC_COMPUTE_INT8) {
+    // the four projections of every layer on the i8 MFMA: their fp16 inputs quantised per
+    // row (the LayerNorm outputs in the LayerNorm's own pass), everything else as below
+    w->ws_q8.ensure((size_t)M * 4 * d);
+    w->ws_qs.ensure(sizeof(float) * M);
+    int8_t* q8 = w->ws_q8.as<int8_t>();
+    float* qs = w->ws_qs.as<float>();
+    auto gemm8 = [&](int epi, int64_t K, const DevMem& W, const DevMem& ws, const float* bias, void* C,
+                     int64_t N, const float* R) {
+      GemmI8Args g;
+      g.A = reinterpret_cast<const signed char*>(q8); g.lda = K;
+      g.W = W.as<signed char>(); g.ldw = K;
+      g.a_scale = qs; g.w_scale = ws.as<float>(); g.bias = bias;
+      g.C = C; g.ldc = N; g.R = R; g.ldr = N; g.M = (int)M; g.N = (int)N; g.K = (int)K;
+      gemm_i8_launch(epi, g, s);
+    };
+    for (int l = 0; l < c.enc_layers; ++l) {
+      EncLayer& L = w->enc[l];
+      layernorm_quant_i8_launch(r, L.ln1g, L.ln1b, q8, qs, (int)M, d, 1e-5f, s);
+      gemm8(EPI_F16, d, L.qqkv, L.sqkv, L.bqkv.as<float>(), qkv, 3 * d, nullptr);
+      attention_launch(qkv, o, B, Te, H, scale, s);
+      quant_rows_i8_launch(o, d, q8, d, qs, (int)M, d, s);
+      gemm8(EPI_RESID_F32, d, L.qo, L.so, L.bo, r, d, r);
+      layernorm_quant_i8_launch(r, L.ln2g, L.ln2b, q8, qs, (int)M, d, 1e-5f, s);
+      gemm8(EPI_GELU_F16, d, L.q1, L.s1, L.b1, f, 4 * d, nullptr);
+      quant_rows_i8_launch(f, 4 * d, q8, 4 * d, qs, (int)M, 4 * d, s);
+      gemm8(EPI_RESID_F32, 4 * d, L.q2, L.s2, L.b2, r, d, r);
+    }
+    layernorm_launch(r, w->params.get("encoder.layer_norm.weight", d),
+                     w->params.get("encoder.layer_norm.bias", d), out, (int)M, d, 1e-5f, s);
+    return;
+  }
   for (int l = 0; l < c.enc_layers; ++l) {
     EncLayer& L = w->enc[l];
     layernorm_launch(r, L.ln1g, L.ln1b, a, (int)M, d, 1e-5f, s);
@@ -1098,7 +1170,28 @@ extern "C" int janus_whisper_encode(janus_whisper* w, const uint16_t* mel, int b
     std::lock_guard<std::mutex> lk(w->mu);
     hipStream_t s = (hipStream_t)stream;
     prepare(w, s);
+    if (w->enc_compute == JANUS_ENC_COMPUTE_INT8) prepare_i8(w, s);
     encode(w, reinterpret_cast<const _Float16*>(mel), batch, reinterpret_cast<_Float16*>(enc), s);
+  });
+}
+
+extern "C" int janus_whisper_set_encoder_compute(janus_whisper* w, int mode) {
+  return guarded([&] {
+    JANUS_CHECK(w, "null argument");
+    JANUS_CHECK(mode == JANUS_ENC_COMPUTE_F16 || mode == JANUS_ENC_COMPUTE_INT8,
+                "encoder compute: 0 (float16) or 1 (int8)");
+    if (mode == JANUS_ENC_COMPUTE_INT8)
+      JANUS_CHECK(w->cfg.d_model % 128 == 0, "int8 encoder: d_model must be a multiple of 128");
+    std::lock_guard<std::mutex> lk(w->mu);
+    w->enc_compute = mode;
+  });
+}
+
+extern "C" int janus_whisper_encoder_compute(janus_whisper* w, int32_t* mode) {
+  return guarded([&] {
+    JANUS_CHECK(w && mode, "null argument");
+    std::lock_guard<std::mutex> lk(w->mu);
+    *mode = w->enc_compute;
   });
 }
 

@@ -304,13 +304,15 @@ class JanusPipeline(PacketRenderer):
     def __init__(self, model: str = "base.en", whisper_seed: int = 0, vocoder_seed: int = 0,
                  max_length: int = 448, vocoder_cfg: FireflyConfig = FireflyConfig(),
                  temperatures=TEMPERATURES, tuning: Optional[ServingTuning] = None,
-                 vocoder_weights: dict = None):
+                 vocoder_weights: dict = None, whisper_compute: str = "float16"):
         """temperatures: faster-whisper's fallback schedule (the default, as the
         reference's transcribe_buffer runs it); (0.0,) decodes each window once at T = 0
         and only reports the gates (bench.py's headline setting on synthetic weights,
-        whose windows all fail the gates: DESIGN.md §0)."""
+        whose windows all fail the gates: DESIGN.md §0).
+        whisper_compute: "float16" (default) or "int8", the compute type of the Whisper
+        encoder's linear layers (WhisperEngine(encoder_compute=...))."""
         super().__init__(vocoder_cfg, vocoder_seed, vocoder_weights)
-        self.whisper = WhisperEngine(CONFIGS[model], seed=whisper_seed)
+        self.whisper = WhisperEngine(CONFIGS[model], seed=whisper_seed, encoder_compute=whisper_compute)
         self.max_length = max_length
         self.temperatures = tuple(float(t) for t in temperatures)
         # parity tests set this to read the encoder output back (it would otherwise keep

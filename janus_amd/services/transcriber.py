@@ -179,6 +179,20 @@ read_wav_16k = wavio.read_wav_16k  # 16-bit PCM WAV -> f32 @ 16 kHz
 DEVICES = ("cpu", "cuda", "auto")
 COMPUTE_TYPES = ("default", "auto", "int8", "int8_float32", "int8_float16", "int8_bfloat16",
                  "int16", "float16", "bfloat16", "float32")
+# faster-whisper compute types whose linear layers are int8 (CTranslate2 quantisation types)
+INT8_COMPUTE_TYPES = ("int8", "int8_float32", "int8_float16", "int8_bfloat16")
+
+
+def resolve_compute_type(compute_type: str, apply_compute_type: bool = False):
+    """(effective_compute_type, encoder_compute) of WhisperModel for a faster-whisper
+    compute_type: ("int8_float16", "int8") when apply_compute_type is set and the type is one
+    of INT8_COMPUTE_TYPES (int8 encoder linears, fp16 everything else), ("float16",
+    "float16") in every other case. ValueError for a type faster-whisper does not know."""
+    if compute_type not in COMPUTE_TYPES:
+        raise ValueError(f"unsupported compute_type {compute_type!r}")
+    if apply_compute_type and compute_type in INT8_COMPUTE_TYPES:
+        return "int8_float16", "int8"
+    return "float16", "float16"
 
 
 def compression_ratio(text: str) -> float:
@@ -476,22 +490,31 @@ class WhisperModel:
 
     Accepts faster-whisper's constructor arguments, including the reference's
     ``device='cpu', compute_type='int8'`` (transcriber.py:23-27), and maps every
-    combination onto the one engine this build has: the gfx950 HIP kernels on the
-    current device, with fp16 weights on MFMA and fp32 accumulation. ``device`` and
-    ``compute_type`` are recorded (``requested_device`` / ``requested_compute_type``)
-    but select nothing: there is no CPU path (the product fails loudly without a GPU)."""
+    combination onto the engine this build has: the gfx950 HIP kernels on the current
+    device. Both arguments are recorded (``requested_device`` / ``requested_compute_type``).
+    ``device`` selects nothing: there is no CPU path (the product fails loudly without a
+    GPU).
+
+    ``compute_type`` selects the encoder's compute type, and only when the caller passes
+    ``apply_compute_type=True``: then ``int8``, ``int8_float16``, ``int8_float32`` and
+    ``int8_bfloat16`` run the encoder's linear layers (QKV, out_proj, fc1, fc2) in int8 on
+    the i8 MFMA with CTranslate2's row-wise symmetric quantisation, and every other accepted
+    value runs them in fp16. The conv stem, attention, LayerNorms and the whole decoder are
+    fp16 weights on MFMA with fp32 accumulation in every case. With the
+    default ``apply_compute_type=False`` every ``compute_type`` runs fp16 — what
+    ``Transcriber`` gets, whose parity tests against the fp32 oracle depend on it.
+    ``effective_compute_type`` reports what runs: ``"float16"`` or ``"int8_float16"``."""
 
     def __init__(self, model_size: str, device: str = "auto", compute_type: str = "default",
-                 **_ignored):
+                 *, apply_compute_type: bool = False, **_ignored):
         if model_size not in CONFIGS:
             raise ValueError(f"unknown model size {model_size!r}; one of {sorted(CONFIGS)}")
         if device not in DEVICES:
             raise ValueError(f"unsupported device {device!r}; one of {DEVICES}")
-        if compute_type not in COMPUTE_TYPES:
-            raise ValueError(f"unsupported compute_type {compute_type!r}")
+        self.effective_compute_type, enc_compute = resolve_compute_type(compute_type, apply_compute_type)
         self.model_size = model_size
         self.requested_device, self.requested_compute_type = device, compute_type
-        self.engine = WhisperEngine(CONFIGS[model_size])
+        self.engine = WhisperEngine(CONFIGS[model_size], encoder_compute=enc_compute)
         self.stats = {"windows": 0, "needs_fallback": 0, "no_speech_skips": 0, "fallback_decodes": 0}
 
     def transcribe(self, audio, beam_size: int = 1, language: str = "en",

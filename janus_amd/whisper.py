@@ -262,10 +262,28 @@ def checkpoint_layers(W: dict, side: str) -> int:
 
 
 # --------------------------------------------------------------------- engine
-class WhisperEngine:
-    """One janus_whisper context on the current GPU (thread-safe per call in C++)."""
+# compute types of the encoder's linear layers (janus.h JANUS_ENC_COMPUTE_*)
+ENCODER_COMPUTE = {"float16": 0, "int8": 1}
 
-    def __init__(self, cfg: WhisperConfig, weights: dict = None, seed: int = 0):
+
+def encoder_compute_mode(name) -> int:
+    """"float16" / "int8" -> JANUS_ENC_COMPUTE_*; ValueError for anything else."""
+    if not isinstance(name, str) or name not in ENCODER_COMPUTE:
+        raise ValueError(f"encoder_compute must be one of {sorted(ENCODER_COMPUTE)}, not {name!r}")
+    return ENCODER_COMPUTE[name]
+
+
+class WhisperEngine:
+    """One janus_whisper context on the current GPU (thread-safe per call in C++).
+
+    encoder_compute: "float16" (default: fp16 weights and activations on the fp16 MFMA) or
+    "int8" (the encoder's QKV / out_proj / fc1 / fc2 on the i8 MFMA with row-wise symmetric
+    quantisation, CTranslate2's int8 compute type). The decoder is fp16 in
+    both."""
+
+    def __init__(self, cfg: WhisperConfig, weights: dict = None, seed: int = 0,
+                 encoder_compute: str = "float16"):
+        mode = encoder_compute_mode(encoder_compute)
         self.device = nat.require_gpu()
         self.cfg = cfg
         self.tokenizer = tok.load_tokenizer()
@@ -282,6 +300,20 @@ class WhisperEngine:
         for name, arr in weights.items():
             a = np.ascontiguousarray(arr, dtype=np.float32)
             nat.call("janus_whisper_set_tensor", self._h, name.encode(), a.ctypes.data, a.size)
+        if mode != ENCODER_COMPUTE["float16"]:
+            nat.call("janus_whisper_set_encoder_compute", self._h, mode)
+
+    @property
+    def encoder_compute(self) -> str:
+        """The compute type the next encode() runs its linear layers in."""
+        m = ctypes.c_int32(-1)
+        nat.call("janus_whisper_encoder_compute", self._h, ctypes.addressof(m))
+        return {v: k for k, v in ENCODER_COMPUTE.items()}[m.value]
+
+    def set_encoder_compute(self, mode: str) -> None:
+        """Switch the encoder's linear layers between "float16" and "int8" (either direction,
+        between calls); the int8 weights are quantised on the first int8 encode()."""
+        nat.call("janus_whisper_set_encoder_compute", self._h, encoder_compute_mode(mode))
 
     def set_tensor(self, name: str, arr) -> None:
         """Re-upload one parameter (janus_whisper_set_tensor); the next call re-prepares
