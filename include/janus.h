@@ -414,6 +414,39 @@ int janus_whisper_decode_sample_rows_ex(janus_whisper* w, const uint16_t* enc, i
                                         float* no_speech_prob, void* stream);
 
 /*
+ * Beam search at temperature 0 (faster-whisper's beam_size, 1 .. 8; patience 1): enc
+ * [n_windows][1500][d], rows->prompts / prompt_lens one prompt per WINDOW (null rows or null
+ * prompts: opt->prompt for every window; rows->enc_index and pos_offset must be null, the
+ * call builds the windows x beam_size decoder rows and their shared encoder rows itself).
+ * Outputs one row per window: tokens [n_windows][max_length], n_tokens, sum_logprob,
+ * no_speech_prob [n_windows]. n_windows * beam_size <= 512; a `persistent` request runs
+ * the launch path. CTranslate2's beam search cannot be pinned offline; the rule built here,
+ * per window with k = beam_size:
+ *  1. Up to k live beams, each with its sampled tokens, cumulative score S (the sum of the
+ *     untempered rule-filtered log-probs, as the greedy sum_logprob) and rule state; a list
+ *     of at most k finished hypotheses. At the first sampled position only beam 0 is live.
+ *  2. Every live beam's log-probs come from the decoding rules applied to its own tokens
+ *     (suppress list, SuppressBlank, timestamp rules, max_initial_timestamp and the
+ *     timestamp-mass rule, which renormalises over the timestamps).
+ *  3. Candidates (S_b + lp_b[v], b, v) over live beams and allowed tokens: the best 2k,
+ *     ordered by score descending, then smaller b, then smaller v.
+ *  4. Walked in order: v == eot is appended to the finished list while it holds fewer than k,
+ *     with normalised score S / n^length_penalty (n = sampled tokens incl. eot); any other
+ *     candidate becomes the next live beam until k are filled, then the walk stops. A child
+ *     inherits its parent's tokens, rule state and self-attention K / V rows.
+ *  5. The window stops when its finished list holds k, or at max_length, where the live
+ *     beams close as they stand with S / (n + 1)^length_penalty.
+ *  6. The finished hypothesis with the highest normalised score wins (earliest on ties); if
+ *     none finished, the best closed live beam. no_speech_prob is beam 0's first step's.
+ * beam_size 1 is the greedy decode.
+ */
+int janus_whisper_decode_beam_ex(janus_whisper* w, const uint16_t* enc, int n_windows,
+                                 const janus_decode_options* opt, const janus_decode_rows* rows,
+                                 int beam_size, float length_penalty, int32_t* tokens,
+                                 int32_t* n_tokens, float* sum_logprob, float* no_speech_prob,
+                                 void* stream);
+
+/*
  * Shape of the last decode call on this context (lane 0): positions the decoder stepped
  * (every row together; the early-exit poll stops at a 16-position boundary) and the
  * kernel launches those positions issued (nodes of the captured decode graphs; 0 when

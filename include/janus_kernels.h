@@ -190,6 +190,49 @@ int janus_np_voiced_mean_f32(const float* values, const int64_t* offsets, int ba
 int janus_sample_gumbel_f32(const uint32_t* seeds, int batch, int pos, int V, float* out,
                             void* stream);
 
+/*
+ * Beam search kernels (janus_whisper_decode_beam_ex), one test entry each. Device pointers.
+ *
+ * janus_beam_partial_blocks: partials per row the vocabulary projection writes for this
+ * shape (returns the count, not a status).
+ *
+ * janus_beam_logits_topk_f16: the beam instantiation of the vocabulary projection —
+ * logits = A[batch][K] . W[V][K]^T (fp16, K = 384 / 512 / 768) filtered by the decoding
+ * rules (smask: V suppress bytes padded to a multiple of 16; row_rules [batch][8] int32 =
+ * sample_begin, suppress_all_ts, suppress_text, ts_floor, last_stamp, 3 pad) with no logits
+ * in memory: parts [batch][nblk] x 56 B (m_all, s_all, m_text, m_ts, s_ts, b_all_v, b_all_i,
+ * b_ts_v, b_ts_i, t_v, m_raw, s_raw, b_all_r, b_ts_r) and tops [batch][nblk] x 256 B (16
+ * logits + 16 indices over every allowed token, then the same over allowed timestamps;
+ * sorted, first index on ties, unused = -inf / 0x7fffffff), then merged per row into the
+ * best n2k (<= 16) of both sets: all_v / all_i / ts_v / ts_i [batch][n2k] (unused: -inf / -1).
+ *
+ * janus_beam_step: one selection step of n_windows windows x beam_size rows at position
+ * pos from hand-built partials (rule of janus_whisper_decode_beam_ex, 3 - 5): tokens
+ * [rows][ld], done / sum_lp / n_tok / plen / row_rules per row, nlive / nfin / wdone / moved
+ * per window, parent per row, fin_tok [windows][beam_size][ld], fin_s / fin_n
+ * [windows][beam_size].
+ *
+ * janus_beam_reorder_f16: kc / vc [layers][n_windows * beam_size][n_ctx][d] fp16 — row i of
+ * every window whose moved flag is set takes positions 0 .. pos of row parent[i] of the same
+ * window, in place.
+ */
+int janus_beam_partial_blocks(int V, int K, int max_blocks);
+int janus_beam_logits_topk_f16(const uint16_t* A, const uint16_t* W, int K, int V, int batch,
+                               int eot, int suppress_blank, int blank, int ts_begin,
+                               int no_timestamps, int max_initial_ts, const uint8_t* smask,
+                               const int32_t* row_rules, int max_blocks, void* parts, void* tops,
+                               int n2k, float* all_v, int32_t* all_i, float* ts_v, int32_t* ts_i,
+                               void* stream);
+int janus_beam_step(const void* parts, const void* tops, int nblk, int eot, int suppress_blank,
+                    int blank, int ts_begin, int no_timestamps, int max_initial_ts,
+                    int32_t* row_rules, int32_t* tokens, int ld, int pos, int32_t* done,
+                    float* sum_lp, int32_t* n_tok, const int32_t* plen, int beam_size,
+                    int n_windows, int32_t* nlive, int32_t* nfin, int32_t* wdone, int32_t* moved,
+                    int32_t* parent, int32_t* fin_tok, float* fin_s, int32_t* fin_n, void* stream);
+int janus_beam_reorder_f16(uint16_t* kc, uint16_t* vc, int layers, int n_windows, int beam_size,
+                           int n_ctx, int d, int pos, const int32_t* parent, const int32_t* moved,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

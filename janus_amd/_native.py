@@ -81,6 +81,7 @@ SIGNATURES = {
     "janus_whisper_decode_greedy_ex": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
     "janus_whisper_decode_sample_ex": [_P, _P, _I32, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P],
     "janus_whisper_decode_sample_rows_ex": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "janus_whisper_decode_beam_ex": [_P, _P, _I32, _P, _P, _I32, _F32, _P, _P, _P, _P, _P],
     "janus_whisper_decode_check": [_P, _I32],
     "janus_whisper_decode_info": [_P, _P, _P],
     "janus_whisper_decode_path": [_P, _P, _P],
@@ -119,6 +120,13 @@ SIGNATURES = {
     "janus_cross_attention_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P],
     "janus_decode_attention_f16": [_P, _I64, _P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _F32,
                                    _P, _P, _P],
+    # beam search kernels (janus_beam_partial_blocks returns a count, not a status)
+    "janus_beam_partial_blocks": [_I32, _I32, _I32],
+    "janus_beam_logits_topk_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P,
+                                   _I32, _P, _P, _I32, _P, _P, _P, _P, _P],
+    "janus_beam_step": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P,
+                        _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "janus_beam_reorder_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
 }
 RESTYPES = {"janus_conv1d_packed_size": ctypes.c_int64}
 

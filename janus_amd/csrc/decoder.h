@@ -39,6 +39,17 @@ struct LogitPart {
   float b_all_r, b_ts_r;  // the logits of b_all_i / b_ts_i (= b_*_v when greedy)
 };
 
+// Beam search: per (row, block) the best kBeamTop allowed entries of the block's columns
+// beside its LogitPart, sorted (logit descending, first index on ties); unused slots hold
+// (-inf, 0x7fffffff). Two sets, because which applies is known only once the whole row's
+// timestamp-mass rule is evaluated: every allowed token / the allowed timestamps.
+constexpr int kBeamTop = 16;    // 2 * the largest beam size
+constexpr int kBeamMax = 8;
+struct BeamTop {
+  float av[kBeamTop]; int ai[kBeamTop];
+  float tv[kBeamTop]; int ti[kBeamTop];
+};
+
 // Sampling noise (decode at temperature > 0): a counter-based hash of (row seed, position,
 // token), so a row's draws do not depend on its batch neighbours or the tile schedule and
 // the CPU oracle can regenerate them (oracle/whisper.py sample_noise).
@@ -90,7 +101,9 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
                            const float* lnx = nullptr, int ldx = 0, const float* ln_g = nullptr,
                            const float* ln_b = nullptr, int max_blocks = 256,
                            const uint32_t* seeds = nullptr, int pos = 0,
-                           const float* row_inv_temp = nullptr);
+                           const float* row_inv_temp = nullptr, BeamTop* tops = nullptr);
+// tops (nullable, greedy only; [B][nblk]): the beam instantiation — each partial also
+// carries its block's best kBeamTop allowed entries (BeamTop)
 // R.inv_temp > 0: seeds [B] (device) per-row noise seeds, pos = the position whose logits
 // these are (the sampled token goes to pos + 1); row_inv_temp [B] (device, nullable): row
 // b samples at 1 / row_inv_temp[b] instead of R.inv_temp (several temperatures in one call)
@@ -113,5 +126,44 @@ void select_embed_launch(const LogitPart* parts, int nblk, const DecodeRules& R,
 void build_mask_launch(const int32_t* list, int n, uint8_t* mask, int V, hipStream_t s);
 // out [B][V] = sample_gumbel(noise_base(seeds[b], pos), t)
 void sample_gumbel_launch(const uint32_t* seeds, int B, int pos, int V, float* out, hipStream_t s);
+
+// ------------------------------------------------------------------ beam search (beam.hip)
+// Device state of a beam decode: rows are windows x k (row w * k + j = beam j of window w).
+struct BeamState {
+  int k;                    // beam size, 1 .. kBeamMax
+  float length_penalty;
+  int32_t* nlive;           // [W] live beams (1 before a window's first sampled step)
+  int32_t* nfin;            // [W] finished hypotheses
+  int32_t* wdone;           // [W] the window stopped
+  int32_t* moved;           // [W] the last step's parents are not the identity
+  int32_t* parent;          // [W * k] parent beam (0 .. k-1) of each row after the last step
+  int32_t* fin_tok;         // [W][k][ld] finished hypotheses: prompt, sampled tokens incl. eot
+  float* fin_s;             // [W][k] their cumulative scores
+  int32_t* fin_n;           // [W][k] their sampled tokens incl. eot
+};
+void beam_init_launch(const BeamState& st, int W, hipStream_t s);
+// One block per window: the window's rows' partials -> the best 2k candidates (score
+// descending, then beam, then token), the walk (eot candidates finish, the others become the
+// next live beams), the children's tokens / scores / rule states, the finished list and
+// the done flags. Rows inside their prompt keep the forced token with identity parents.
+void beam_step_launch(const LogitPart* parts, const BeamTop* tops, int nblk, const DecodeRules& R,
+                      RowRules* rules, int32_t* tokens, int ld, int pos, int32_t* done,
+                      float* sum_lp, int32_t* n_tok, const int32_t* plen, float* nsp,
+                      const BeamState& st, int W, hipStream_t s);
+// The self-attention caches follow the parents: row i of a window takes positions 0 .. pos
+// of row parent[i], in place (a block loads its slab of every row of the window, then
+// stores). kc / vc: [layers][W * k][n_ctx][d] fp16.
+void beam_reorder_launch(_Float16* kc, _Float16* vc, int layers, int W, int k, int n_ctx, int d,
+                         int pos, const int32_t* parent, const int32_t* moved, hipStream_t s);
+// The winner of every window (finished hypothesis with the best S / n^length_penalty, the
+// earliest on ties; none finished: the best live beam closed at n + 1) -> the call's outputs
+void beam_finish_launch(const BeamState& st, const DecodeRules& R, const int32_t* tokens, int ld,
+                        const float* sum_lp, const int32_t* n_tok, const int32_t* plen,
+                        const float* nsp, int W, int32_t* tokens_out, int32_t* n_tokens_out,
+                        float* sum_lp_out, float* nsp_out, hipStream_t s);
+// kernel test: per row the best n2k entries of both sets merged over the row's nblk partials
+// -> out_*[B][n2k] (unused: -inf / -1)
+void beam_rowtop_launch(const BeamTop* tops, int nblk, int B, int n2k, float* all_v, int32_t* all_i,
+                        float* ts_v, int32_t* ts_i, hipStream_t s);
 
 }  // namespace janus

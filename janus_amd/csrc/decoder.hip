@@ -15,6 +15,7 @@
 #include "mfma.h"
 #include "kernels.h"
 #include "decoder.h"
+#include "decoder_dev.h"
 
 namespace janus {
 
@@ -374,17 +375,7 @@ int logits_partial_blocks(int V, int K, int max_blocks) {
   return std::max(1, std::min(cap, ((V + 15) / 16 + lg_waves(K) - 1) / lg_waves(K)));
 }
 
-__device__ __forceinline__ float lse_merge(float m1, float s1, float m2, float s2, float* mo) {
-  const float m = fmaxf(m1, m2);
-  *mo = m;
-  if (m == -INFINITY) return 0.f;
-  return s1 * __expf(m1 - m) + s2 * __expf(m2 - m);
-}
-
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
-  return v > bv || (v == bv && i < bi);
-}
-
+// (lse_merge / better: decoder_dev.h, shared with the beam kernels)
 // Vocabulary projection + rule-filtered statistics: logits = A[B<=64][K] . W[V][K]^T
 // (W = the token embedding, tied). The 53 MB weight read once per step is the cost: each
 // block stages A (all rows) in LDS once, then its 8 waves walk 16-column tiles
@@ -401,13 +392,17 @@ __device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
 // over the perturbed keys logit * inv_temp + Gumbel noise (Gumbel-max: a draw from
 // softmax(logits / T) over the same rule-filtered set), the chosen logit carried beside
 // the key for the log-probability; everything else as in the greedy kernel.
-template <int NKS, int NB, bool SAMPLE>  // K / 32
+// BEAM (beam search, greedy keys): the row's kBeamTop best allowed entries of this block's
+// columns ride along (BeamTop: every allowed token / the allowed timestamps), kept per lane
+// = row in sorted registers and merged over the 8 waves after the statistics.
+template <int NKS, int NB, bool SAMPLE, bool BEAM = false>  // K / 32
 __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel(
     const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W, int V, int B,
     DecodeRules R, const uint8_t* __restrict__ smask, const RowRules* __restrict__ rules,
     LogitPart* __restrict__ parts, int ntiles, const float* __restrict__ lnx, int ldx,
     const float* __restrict__ ln_g, const float* __restrict__ ln_b, int rot,
-    const uint32_t* __restrict__ seeds, int pos, const float* __restrict__ rinv) {
+    const uint32_t* __restrict__ seeds, int pos, const float* __restrict__ rinv,
+    BeamTop* __restrict__ tops) {
   extern __shared__ __attribute__((aligned(16))) _Float16 lg_smem[];
   JANUS_DEC_WAVE_PRIO();
   // row group blockIdx.y: rows [64 y, 64 y + 64) of the call (one launch for every group:
@@ -420,6 +415,7 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
     if (lnx) lnx += (int64_t)r0 * ldx;
     if (seeds) seeds += r0;
     if (rinv) rinv += r0;
+    if (BEAM) tops += (int64_t)r0 * gridDim.x;
     B = min(64, B - r0);
   }
   constexpr int K = NKS * 32;
@@ -489,6 +485,25 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
   float ba_r = -INFINITY, bt_r = -INFINITY;                // logits of the sampled argmaxes
   uint32_t nb = 0;                                         // row's noise base at this position
   if constexpr (SAMPLE) nb = noise_base(lane < B ? seeds[lane] : 0u, pos);
+  // BEAM: sorted best lists of row = lane (static indices only: they stay in registers)
+  float la_v[kBeamTop], lt_v[kBeamTop];
+  int la_i[kBeamTop], lt_i[kBeamTop];
+  if constexpr (BEAM) {
+#pragma unroll
+    for (int q = 0; q < kBeamTop; ++q) { la_v[q] = lt_v[q] = -INFINITY; la_i[q] = lt_i[q] = 0x7fffffff; }
+  }
+  auto beam_ins = [&](float (&lv)[kBeamTop], int (&li)[kBeamTop], float v, int t)
+      __attribute__((always_inline)) {
+    if (!better(v, t, lv[kBeamTop - 1], li[kBeamTop - 1])) return;
+#pragma unroll
+    for (int q = 0; q < kBeamTop; ++q) {
+      const bool bt = better(v, t, lv[q], li[q]);
+      const float ov = lv[q];
+      const int oi = li[q];
+      lv[q] = bt ? v : ov; li[q] = bt ? t : oi;
+      v = bt ? ov : v; t = bt ? oi : t;
+    }
+  };
   for (int tb = tile0; tb < ntiles; tb += NB * stride) {
 #pragma unroll
   for (int u = 0; u < NB; ++u) {
@@ -573,6 +588,11 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
 #pragma unroll
         for (int c = 0; c < 16; ++c)
           if (((okm >> c) & 1u) && better(vals[c], col0 + c, ba_v, ba_i)) { ba_v = vals[c]; ba_i = col0 + c; }
+        if constexpr (BEAM) {
+#pragma unroll
+          for (int c = 0; c < 16; ++c)
+            if ((okm >> c) & 1u) beam_ins(la_v, la_i, vals[c], col0 + c);
+        }
       }
     } else {
 #pragma unroll
@@ -603,9 +623,11 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
         // sampling: the key (perturbed logit) is compared, the logit kept beside it
         const float key = SAMPLE && inv_t > 0.f ? v * inv_t + sample_gumbel(nb, t) : v;
         if (better(key, t, ba_v, ba_i)) { ba_v = key; ba_i = t; ba_r = v; }
+        if constexpr (BEAM) beam_ins(la_v, la_i, v, t);
         if (R.ts_begin >= 0 && t >= R.ts_begin) {
           u_ts += __expf(v - t_ts);
           if (better(key, t, bt_v, bt_i)) { bt_v = key; bt_i = t; bt_r = v; }
+          if constexpr (BEAM) beam_ins(lt_v, lt_i, v, t);
         }
       }
     }
@@ -643,6 +665,51 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
     }
     parts[(int64_t)lane * gridDim.x + blockIdx.x] = q;
   }
+  if constexpr (BEAM) {
+    // the 8 waves' sorted lists of each row -> the block's best kBeamTop, one set at a time
+    // through LDS ([wave][slot][row]: 64 KB over the A tile and the patches, both done with)
+    float* mv = reinterpret_cast<float*>(lg_smem);
+    int* mi = reinterpret_cast<int*>(mv + kLgWaves * kBeamTop * 64);
+    BeamTop* dst = tops + (int64_t)lane * gridDim.x + blockIdx.x;
+#pragma unroll
+    for (int set = 0; set < 2; ++set) {
+      __syncthreads();  // the previous user of this LDS (wave partials / the other set) is done
+#pragma unroll
+      for (int q = 0; q < kBeamTop; ++q) {
+        mv[(w * kBeamTop + q) * 64 + lane] = set ? lt_v[q] : la_v[q];
+        mi[(w * kBeamTop + q) * 64 + lane] = set ? lt_i[q] : la_i[q];
+      }
+      __syncthreads();
+      if (w == 0 && lane < B) {
+        float hv[kLgWaves];
+        int hi[kLgWaves], hp[kLgWaves];
+#pragma unroll
+        for (int k = 0; k < kLgWaves; ++k) {
+          hp[k] = 0;
+          hv[k] = mv[(k * kBeamTop) * 64 + lane];
+          hi[k] = mi[(k * kBeamTop) * 64 + lane];
+        }
+        for (int q = 0; q < kBeamTop; ++q) {
+          float bv = hv[0];
+          int bi = hi[0], bk = 0;
+#pragma unroll
+          for (int k = 1; k < kLgWaves; ++k)
+            if (better(hv[k], hi[k], bv, bi)) { bv = hv[k]; bi = hi[k]; bk = k; }
+          if (set) { dst->tv[q] = bv; dst->ti[q] = bi; }
+          else { dst->av[q] = bv; dst->ai[q] = bi; }
+#pragma unroll
+          for (int k = 0; k < kLgWaves; ++k)
+            if (k == bk) {
+              hp[k] += 1;
+              const bool in = hp[k] < kBeamTop;
+              const int o = (k * kBeamTop + (in ? hp[k] : 0)) * 64 + lane;
+              hv[k] = in ? mv[o] : -INFINITY;
+              hi[k] = in ? mi[o] : 0x7fffffff;
+            }
+        }
+      }
+    }
+  }
 }
 #undef LG_LOAD
 #undef LG_WLD
@@ -651,7 +718,8 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
                            const DecodeRules& R, const uint8_t* smask, const RowRules* rules,
                            LogitPart* parts, hipStream_t s, const float* lnx, int ldx,
                            const float* ln_g, const float* ln_b, int max_blocks,
-                           const uint32_t* seeds, int pos, const float* row_inv_temp) {
+                           const uint32_t* seeds, int pos, const float* row_inv_temp, BeamTop* tops) {
+  JANUS_CHECK(!tops || !(R.inv_temp > 0.f), "logits: the beam partials are greedy only");
   JANUS_CHECK(K == 384 || K == 512 || K == 768, "logits: K (d_model) must be 384, 512 or 768");
   const bool sample = R.inv_temp > 0.f;
   JANUS_CHECK(!sample || seeds, "logits: sampling needs per-row seeds");
@@ -660,14 +728,16 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
   const size_t lds = (size_t)64 * (K + 16) * 2 + (size_t)nw * 64 * 17 * 4 + 64 * sizeof(RowRules);
   // weight tiles in flight per wave (JANUS_LG_DEPTH=2: two)
   static const int depth = ab_env("JANUS_LG_DEPTH") ? std::atoi(ab_env("JANUS_LG_DEPTH")) : 1;
-  auto kern = sample ? (K == 384 ? logits_partial_kernel<12, 1, true> : K == 512 ? logits_partial_kernel<16, 1, true>
+  auto kern = tops ? (K == 384 ? logits_partial_kernel<12, 1, false, true> : K == 512 ? logits_partial_kernel<16, 1, false, true>
+                                                                        : logits_partial_kernel<24, 1, false, true>)
+              : sample ? (K == 384 ? logits_partial_kernel<12, 1, true> : K == 512 ? logits_partial_kernel<16, 1, true>
                                                                           : logits_partial_kernel<24, 1, true>)
               : depth > 1 ? (K == 384 ? logits_partial_kernel<12, 2, false> : K == 512 ? logits_partial_kernel<16, 2, false>
                                                                             : logits_partial_kernel<24, 1, false>)
                         : (K == 384 ? logits_partial_kernel<12, 1, false> : K == 512 ? logits_partial_kernel<16, 1, false>
                                                                             : logits_partial_kernel<24, 1, false>);
-  static bool attr[9] = {false, false, false, false, false, false, false, false, false};
-  const int ai = (K == 384 ? 0 : K == 512 ? 1 : 2) + (sample ? 6 : depth > 1 ? 3 : 0);
+  static bool attr[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
+  const int ai = (K == 384 ? 0 : K == 512 ? 1 : 2) + (tops ? 9 : sample ? 6 : depth > 1 ? 3 : 0);
   if (!attr[ai]) {
     JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024));
@@ -694,7 +764,7 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
   // 64 rows per row group (blockIdx.y), every group in one launch
   kern<<<dim3(grid, (B + 63) / 64), nw * 64, lds, s>>>(A, lda, W, V, B, R, smask, rules, parts, ntiles, lnx, ldx,
                                                       ln_g, ln_b, rot, seeds, pos,
-                                                      sample ? row_inv_temp : nullptr);
+                                                      sample ? row_inv_temp : nullptr, tops);
   JANUS_LAUNCH_CHECK();
 }
 
@@ -724,67 +794,12 @@ __device__ __forceinline__ int select_row(
     if (tid == 0) row_tok[pos + 1] = R.eot;
     return R.eot;
   }
-  float m_all = -INFINITY, s_all = 0.f, m_text = -INFINITY, m_ts = -INFINITY, s_ts = 0.f;
-  float ba_v = -INFINITY, bt_v = -INFINITY;
-  int ba_i = 0x7fffffff, bt_i = 0x7fffffff;
-  float m_raw = -INFINITY, s_raw = 0.f, t_v = -INFINITY;
-  float ba_r = -INFINITY, bt_r = -INFINITY;
-  const LogitPart* pr = parts + (int64_t)b * nblk;
-  for (int i = tid; i < nblk; i += 256) {
-    const LogitPart p = pr[i];
-    float mo;
-    s_all = lse_merge(m_all, s_all, p.m_all, p.s_all, &mo); m_all = mo;
-    s_ts = lse_merge(m_ts, s_ts, p.m_ts, p.s_ts, &mo); m_ts = mo;
-    s_raw = lse_merge(m_raw, s_raw, p.m_raw, p.s_raw, &mo); m_raw = mo;
-    m_text = fmaxf(m_text, p.m_text);
-    t_v = fmaxf(t_v, p.t_v);
-    if (better(p.b_all_v, p.b_all_i, ba_v, ba_i)) { ba_v = p.b_all_v; ba_i = p.b_all_i; ba_r = p.b_all_r; }
-    if (better(p.b_ts_v, p.b_ts_i, bt_v, bt_i)) { bt_v = p.b_ts_v; bt_i = p.b_ts_i; bt_r = p.b_ts_r; }
-  }
-  // butterfly over the wave (xshfl: the partner lane's values as __shfl_xor, no LDS trip)
-  auto level = [&](auto shf, auto shi) __attribute__((always_inline)) {
-    float mo;
-    const float om = shf(m_all), os = shf(s_all);
-    s_all = lse_merge(m_all, s_all, om, os, &mo); m_all = mo;
-    const float tm = shf(m_ts), ts = shf(s_ts);
-    s_ts = lse_merge(m_ts, s_ts, tm, ts, &mo); m_ts = mo;
-    const float rm = shf(m_raw), rs = shf(s_raw);
-    s_raw = lse_merge(m_raw, s_raw, rm, rs, &mo); m_raw = mo;
-    m_text = fmaxf(m_text, shf(m_text));
-    t_v = fmaxf(t_v, shf(t_v));
-    const float av = shf(ba_v); const int ai = shi(ba_i);
-    const float ar = shf(ba_r);
-    if (better(av, ai, ba_v, ba_i)) { ba_v = av; ba_i = ai; ba_r = ar; }
-    const float tv = shf(bt_v); const int ti = shi(bt_i);
-    const float tr = shf(bt_r);
-    if (better(tv, ti, bt_v, bt_i)) { bt_v = tv; bt_i = ti; bt_r = tr; }
-  };
-  level([](float x) { return xshfl<32>(x); }, [](int x) { return xshfl_i<32>(x); });
-  level([](float x) { return xshfl<16>(x); }, [](int x) { return xshfl_i<16>(x); });
-  level([](float x) { return xshfl<8>(x); }, [](int x) { return xshfl_i<8>(x); });
-  level([](float x) { return xshfl<4>(x); }, [](int x) { return xshfl_i<4>(x); });
-  level([](float x) { return xshfl<2>(x); }, [](int x) { return xshfl_i<2>(x); });
-  level([](float x) { return xshfl<1>(x); }, [](int x) { return xshfl_i<1>(x); });
-  if (lane == 0) {
-    LogitPart p;
-    p.m_all = m_all; p.s_all = s_all; p.m_text = m_text; p.m_ts = m_ts; p.s_ts = s_ts;
-    p.b_all_v = ba_v; p.b_all_i = ba_i; p.b_ts_v = bt_v; p.b_ts_i = bt_i;
-    p.t_v = t_v; p.m_raw = m_raw; p.s_raw = s_raw; p.b_all_r = ba_r; p.b_ts_r = bt_r;
-    sh[w] = p;
-  }
-  __syncthreads();
+  // the row's partials merged (decoder_dev.h: the same reduction the beam step runs)
+  const LogitPart q = row_parts_reduce(parts + (int64_t)b * nblk, nblk, sh);
   if (tid != 0) return -1;
-  for (int k = 1; k < 4; ++k) {
-    const LogitPart& p = sh[k];
-    float mo;
-    s_all = lse_merge(m_all, s_all, p.m_all, p.s_all, &mo); m_all = mo;
-    s_ts = lse_merge(m_ts, s_ts, p.m_ts, p.s_ts, &mo); m_ts = mo;
-    s_raw = lse_merge(m_raw, s_raw, p.m_raw, p.s_raw, &mo); m_raw = mo;
-    m_text = fmaxf(m_text, p.m_text);
-    t_v = fmaxf(t_v, p.t_v);
-    if (better(p.b_all_v, p.b_all_i, ba_v, ba_i)) { ba_v = p.b_all_v; ba_i = p.b_all_i; ba_r = p.b_all_r; }
-    if (better(p.b_ts_v, p.b_ts_i, bt_v, bt_i)) { bt_v = p.b_ts_v; bt_i = p.b_ts_i; bt_r = p.b_ts_r; }
-  }
+  const float m_all = q.m_all, s_all = q.s_all, m_text = q.m_text, m_ts = q.m_ts, s_ts = q.s_ts;
+  const float m_raw = q.m_raw, s_raw = q.s_raw, t_v = q.t_v, ba_r = q.b_all_r, bt_r = q.b_ts_r;
+  const int ba_i = q.b_all_i, bt_i = q.b_ts_i;
   // no_speech_prob: the raw softmax probability of the target token at the row's first
   // sampled step (logits at the <|startoftranscript|> position, before any filter)
   if (nsp && pos + 1 == pl) nsp[b] = R.target >= 0 ? __expf(t_v - (m_raw + __logf(s_raw))) : 0.f;
@@ -804,15 +819,7 @@ __device__ __forceinline__ int select_row(
   n_tok[b] += 1;
   if (next == R.eot) done[b] = 1;
   // rules for the next step
-  RowRules r = rules[b];
-  const bool last_ts = R.ts_begin >= 0 && next >= R.ts_begin;
-  const bool pen_ts = r.sample_begin || (R.ts_begin >= 0 && row_tok[pos] >= R.ts_begin);
-  r.sample_begin = 0;
-  r.suppress_all_ts = last_ts && pen_ts;
-  r.suppress_text = last_ts && !pen_ts;
-  if (last_ts) r.last_stamp = next;
-  r.ts_floor = r.last_stamp >= 0 ? ((last_ts && !pen_ts) ? r.last_stamp : r.last_stamp + 1) : -1;
-  rules[b] = r;
+  rules[b] = next_row_rules(rules[b], R, row_tok[pos], next);
   return next;
 }
 

@@ -240,3 +240,69 @@ extern "C" int janus_sample_gumbel_f32(const uint32_t* seeds, int batch, int pos
     sample_gumbel_launch(seeds, batch, pos, V, out, (hipStream_t)stream);
   });
 }
+
+// ------------------------------------------------------------------ beam search
+static DecodeRules beam_rules(int eot, int suppress_blank, int blank, int ts_begin, int no_timestamps,
+                              int max_initial_ts) {
+  DecodeRules R;
+  R.eot = eot; R.suppress_blank = suppress_blank; R.blank = blank; R.ts_begin = ts_begin;
+  R.no_timestamps = no_timestamps; R.max_initial_ts = max_initial_ts; R.target = -1; R.inv_temp = 0.f;
+  return R;
+}
+
+extern "C" int janus_beam_partial_blocks(int V, int K, int max_blocks) {
+  return logits_partial_blocks(V, K, max_blocks);
+}
+
+extern "C" int janus_beam_logits_topk_f16(const uint16_t* A, const uint16_t* W, int K, int V, int batch,
+                                          int eot, int suppress_blank, int blank, int ts_begin,
+                                          int no_timestamps, int max_initial_ts, const uint8_t* smask,
+                                          const int32_t* row_rules, int max_blocks, void* parts,
+                                          void* tops, int n2k, float* all_v, int32_t* all_i, float* ts_v,
+                                          int32_t* ts_i, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(A && W && smask && row_rules && parts && tops && all_v && all_i && ts_v && ts_i, "null argument");
+    JANUS_CHECK(batch >= 1 && batch <= kSkinnyMaxRows, "beam_logits_topk: 1 <= batch <= 512");
+    static_assert(sizeof(RowRules) == 32 && sizeof(LogitPart) == 56 && sizeof(BeamTop) == 256, "ABI sizes");
+    const DecodeRules R = beam_rules(eot, suppress_blank, blank, ts_begin, no_timestamps, max_initial_ts);
+    const int nblk = logits_partial_blocks(V, K, max_blocks);
+    logits_partial_launch(reinterpret_cast<const _Float16*>(A), K, reinterpret_cast<const _Float16*>(W), K, V,
+                          batch, R, smask, reinterpret_cast<const RowRules*>(row_rules),
+                          static_cast<LogitPart*>(parts), (hipStream_t)stream, nullptr, 0, nullptr, nullptr,
+                          max_blocks, nullptr, 0, nullptr, static_cast<BeamTop*>(tops));
+    beam_rowtop_launch(static_cast<const BeamTop*>(tops), nblk, batch, n2k, all_v, all_i, ts_v, ts_i,
+                       (hipStream_t)stream);
+  });
+}
+
+extern "C" int janus_beam_step(const void* parts, const void* tops, int nblk, int eot, int suppress_blank,
+                               int blank, int ts_begin, int no_timestamps, int max_initial_ts,
+                               int32_t* row_rules, int32_t* tokens, int ld, int pos, int32_t* done,
+                               float* sum_lp, int32_t* n_tok, const int32_t* plen, int beam_size,
+                               int n_windows, int32_t* nlive, int32_t* nfin, int32_t* wdone,
+                               int32_t* moved, int32_t* parent, int32_t* fin_tok, float* fin_s,
+                               int32_t* fin_n, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(parts && tops && row_rules && tokens && done && sum_lp && n_tok && plen && nlive && nfin &&
+                    wdone && moved && parent && fin_tok && fin_s && fin_n, "null argument");
+    JANUS_CHECK(n_windows >= 1, "beam_step: n_windows must be >= 1");
+    const DecodeRules R = beam_rules(eot, suppress_blank, blank, ts_begin, no_timestamps, max_initial_ts);
+    BeamState st{};
+    st.k = beam_size; st.length_penalty = 1.0f;
+    st.nlive = nlive; st.nfin = nfin; st.wdone = wdone; st.moved = moved; st.parent = parent;
+    st.fin_tok = fin_tok; st.fin_s = fin_s; st.fin_n = fin_n;
+    beam_step_launch(static_cast<const LogitPart*>(parts), static_cast<const BeamTop*>(tops), nblk, R,
+                     reinterpret_cast<RowRules*>(row_rules), tokens, ld, pos, done, sum_lp, n_tok, plen,
+                     nullptr, st, n_windows, (hipStream_t)stream);
+  });
+}
+
+extern "C" int janus_beam_reorder_f16(uint16_t* kc, uint16_t* vc, int layers, int n_windows, int beam_size,
+                                      int n_ctx, int d, int pos, const int32_t* parent,
+                                      const int32_t* moved, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(kc && vc && parent && moved, "null argument");
+    beam_reorder_launch(reinterpret_cast<_Float16*>(kc), reinterpret_cast<_Float16*>(vc), layers, n_windows,
+                        beam_size, n_ctx, d, pos, parent, moved, (hipStream_t)stream);
+  });
+}

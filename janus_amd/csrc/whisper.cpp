@@ -69,7 +69,7 @@ struct DecLane {
   DevMem d_x, d_a, d_qkv, d_o, d_q2, d_f, d_kc, d_vc, d_ck, d_cv, d_smask, d_done, d_prompt, d_nsp,
       d_supp, d_part_o, d_part_ml, d_parts, d_rules, d_tok, d_ntok, d_slp, d_lnp, d_lncnt, d_xqk,
       d_xc, d_xpc, d_xpml, d_enc, d_seed, d_xpairs, d_xgroups, d_roff, d_omid, d_segbar, d_segerr,
-      d_itemp;
+      d_itemp, d_btop, d_bint, d_bfin, d_bfs;   // (beam search: partial tops, window state, finished list)
   std::vector<float> h_itemp;    // per-row 1 / T of the last call (source of an async copy)
   std::map<std::vector<int64_t>, hipGraphExec_t> graphs;
   std::map<std::vector<int64_t>, size_t> graph_nodes;  // kernel nodes per captured graph
@@ -387,6 +387,14 @@ struct DecodeSampling {
   const float* temps = nullptr;   // host [B], per-row temperatures (overrides temperature)
 };
 
+// Beam search (janus_whisper_decode_beam_ex): the call's rows are windows x k, row w * k + j
+// beam j of window w (the entry builds enc_index and the per-row prompts); the selection is
+// the beam step + the KV reorder, and the outputs are one row per window.
+struct BeamMode {
+  int k;
+  float length_penalty;
+};
+
 // The deferred barrier-timeout check of the lane's last non-polling call (check_every 0):
 // waits for that call's flag copy and throws if a persistent segment gave up at a barrier.
 static void lane_check(DecLane& Z) {
@@ -404,7 +412,7 @@ static void lane_check(DecLane& Z) {
 static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, int B, const janus_decode_options* opt,
                           const janus_decode_rows* rows, int32_t* tokens_out, int32_t* n_tokens_out,
                           float* sum_lp_out, float* nsp_out, hipStream_t s, LaneLatch* latch,
-                          const DecodeSampling* smp = nullptr) {
+                          const DecodeSampling* smp = nullptr, const BeamMode* beam = nullptr) {
   lane_check(Z);   // the previous non-polling call's flag first
   LaneArrival arrival(latch);
   const auto& c = w->cfg;
@@ -548,6 +556,13 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
     if (f1 <= f0) f0 = f1 = 0;
     for (int b = f0; b < f1; ++b) JANUS_CHECK(h_roff[b] == 0, "decode: fresh rows must be contiguous");
   }
+  if (beam) {
+    JANUS_CHECK(beam->k >= 1 && beam->k <= kBeamMax && B % beam->k == 0, "decode: beam_size must be 1 .. 8");
+    JANUS_CHECK(!stagger, "decode: beam search does not take staggered rows (pos_offset)");
+    JANUS_CHECK(!(smp && smp->temperature > 0.f), "decode: beam search runs at temperature 0");
+    JANUS_CHECK(B <= kSkinnyMaxRows, "decode: windows x beam_size must be <= 512 rows");
+    JANUS_CHECK(per_row && maxlen <= 448, "decode: beam search needs per-row prompts, max_length <= 448");
+  }
   JANUS_CHECK(!stagger || rows->steps >= 0, "decode: steps must be >= 0");
   const int steps = (stagger && rows->steps > 0) ? rows->steps : maxlen - 1;
   JANUS_CHECK(!stagger || max_roff + steps <= maxlen, "decode: pos_offset + steps > max_length");
@@ -602,6 +617,20 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
   const int nblk = logits_partial_blocks(V, d, lg_cap);
   Z.d_parts.ensure(sizeof(LogitPart) * (int64_t)B * nblk);
   Z.d_rules.ensure(sizeof(RowRules) * B);
+  // beam search: the partials' best entries, the per-window state and the finished list
+  BeamState bst{};
+  const int nwin = beam ? B / beam->k : 0;
+  if (beam) {
+    Z.d_btop.ensure(sizeof(BeamTop) * (int64_t)B * nblk);
+    Z.d_bint.ensure(sizeof(int32_t) * (4 * (int64_t)nwin + 2 * (int64_t)B));
+    Z.d_bfin.ensure(sizeof(int32_t) * (int64_t)B * maxlen);
+    Z.d_bfs.ensure(sizeof(float) * B);
+    int32_t* bi = Z.d_bint.as<int32_t>();
+    bst.k = beam->k; bst.length_penalty = beam->length_penalty;
+    bst.nlive = bi; bst.nfin = bi + nwin; bst.wdone = bi + 2 * nwin; bst.moved = bi + 3 * nwin;
+    bst.parent = bi + 4 * nwin; bst.fin_n = bi + 4 * nwin + B;
+    bst.fin_tok = Z.d_bfin.as<int32_t>(); bst.fin_s = Z.d_bfs.as<float>();
+  }
   float* part_o = Z.d_part_o.as<float>();
   float* part_ml = Z.d_part_ml.as<float>();
   Z.d_done.ensure(sizeof(int32_t) * B);
@@ -655,6 +684,7 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
     init_counters_launch(done + f0, sum_lp + f0, n_tokens + f0, Z.d_nsp.as<float>() + f0, f1 - f0, s);
     rules_init_launch(Z.d_rules.as<RowRules>() + f0, f1 - f0, s);
   }
+  if (beam) beam_init_launch(bst, nwin, s);
 
   // cross-attention: absorbed (stream enc itself, JANUS_DEC_PATH_NO_XABSORB restores per-layer K/V)
   const bool xabs = xattn_supported(d, H) && B <= kSkinnyMaxRows && !path(JANUS_DEC_PATH_NO_XABSORB);
@@ -779,7 +809,8 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
   // the selection at pos and the embedding at pos + 1 in one launch (select_embed_kernel,
   // bit-identical; JANUS_DEC_PATH_NO_SEL_EMBED restores the two launches): a step from the first
   // sampled position on finds its row already embedded by the previous step's selection
-  const bool fuse_se = !path(JANUS_DEC_PATH_NO_SEL_EMBED);
+  // (beam search: the beam step picks the tokens, the next position embeds them itself)
+  const bool fuse_se = !path(JANUS_DEC_PATH_NO_SEL_EMBED) && !beam;
   JANUS_CHECK(!stagger || (!fused_ln && !ln_fuse && !rln && xabs),
               "decode: staggered rows run the default decoder kernels only");
   // persistent segments (dec_persist.hip, janus_decode_options.persistent): per layer the
@@ -791,7 +822,8 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
   // (resident grids need every block co-resident: the kernels' occupancy must admit one
   // block per CU of the partition, and a multi-lane call, whose lanes run concurrently on
   // the same CUs, keeps the launch path)
-  const int seg_grid = opt->persistent && latch == nullptr ? dec_seg_grid(B, cus, path(JANUS_DEC_PATH_SEG_2CU)) : 0;
+  // (beam search runs the launch path: a persistent request falls back, as at d_model 768)
+  const int seg_grid = opt->persistent && latch == nullptr && !beam ? dec_seg_grid(B, cus, path(JANUS_DEC_PATH_SEG_2CU)) : 0;
   const bool persist = seg_grid > 0 && dec_seg_supported(d, H, B, cus) && dec_seg_resident(seg_grid, cus) &&
                        xabs && !shared && !fused_ln && !ln_fuse && !rln && ngroups == 0 && npairs == 0;
   // persistent = 2: segment B of layer l, the self-attention of l + 1 and its segment A as
@@ -982,7 +1014,18 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
                           Z.d_rules.as<RowRules>(), Z.d_parts.as<LogitPart>(), s,
                           lnp_fin ? x : nullptr, d, fin_g, fin_b, lg_cap,
                           sampling ? Z.d_seed.as<uint32_t>() : nullptr, pos,
-                          row_temps ? Z.d_itemp.as<float>() : nullptr);
+                          row_temps ? Z.d_itemp.as<float>() : nullptr,
+                          beam ? Z.d_btop.as<BeamTop>() : nullptr);
+    if (beam) {
+      beam_step_launch(Z.d_parts.as<LogitPart>(), Z.d_btop.as<BeamTop>(), nblk, R, Z.d_rules.as<RowRules>(),
+                       tokens, maxlen, pos, done, sum_lp, n_tokens, Z.d_prompt.as<int32_t>(),
+                       Z.d_nsp.as<float>(), bst, nwin, s);
+      // the children's K / V rows of positions 0 .. pos follow their parents
+      if (pos + 1 < maxlen - 1)
+        beam_reorder_launch(Z.d_kc.as<_Float16>(), Z.d_vc.as<_Float16>(), nl, nwin, beam->k, NC, d, pos,
+                            bst.parent, bst.moved, s);
+      return;
+    }
     if (fuse_se && pos + 1 < maxlen - 1)
       select_embed_launch(Z.d_parts.as<LogitPart>(), nblk, R, Z.d_rules.as<RowRules>(), tokens,
                           maxlen, pos, done, sum_lp, n_tokens, B, s, Z.d_prompt.as<int32_t>(),
@@ -1009,7 +1052,8 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
       (int64_t)Z.d_itemp.p, (int64_t)xpairs,
       (int64_t)npairs, (int64_t)xgroups, (int64_t)ngroups, (int64_t)grp_rows, (int64_t)n_main, (int64_t)rem_rows, (int64_t)roff,
       (int64_t)max_roff, (int64_t)persist + (int64_t)layerk + (int64_t)xfuse, (int64_t)seg_grid, (int64_t)Z.d_omid.p, (int64_t)Z.d_segbar.p,
-      (int64_t)Z.d_segerr.p};
+      (int64_t)Z.d_segerr.p, (int64_t)(beam ? beam->k : 0), (int64_t)Z.d_btop.p, (int64_t)Z.d_bint.p,
+      (int64_t)Z.d_bfin.p, (int64_t)Z.d_bfs.p};
   arrival.now();  // all lanes' allocations done: captures may start
   if (Z.graphs.size() > 512) {
     for (auto& kv : Z.graphs) (void)hipGraphExecDestroy(kv.second);
@@ -1083,6 +1127,12 @@ static void decode_greedy(janus_whisper* w, DecLane& Z, const _Float16* enc_in, 
   Z.stand.assign(B, 0);
   for (int b = 0; b < B; ++b) Z.stand[b] = (stagger ? h_roff[b] : 0) + Z.last_positions;
   Z.stand_maxlen = maxlen;
+  if (beam) {  // one output row per window: its winner
+    Z.stand.clear();  // nothing here is a row a staggered call could continue
+    beam_finish_launch(bst, R, tokens, maxlen, sum_lp, n_tokens, Z.d_prompt.as<int32_t>(), Z.d_nsp.as<float>(),
+                       nwin, tokens_out, n_tokens_out, sum_lp_out, nsp_out, s);
+    return;
+  }
   JANUS_HIP(hipMemcpyAsync(tokens_out, tokens, sizeof(int32_t) * (int64_t)B * maxlen,
                            hipMemcpyDeviceToDevice, s));
   JANUS_HIP(hipMemcpyAsync(n_tokens_out, n_tokens, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, s));
@@ -1205,7 +1255,8 @@ extern "C" int janus_whisper_decode_greedy(janus_whisper* w, const uint16_t* enc
 static int decode_entry(janus_whisper* w, const uint16_t* enc, int batch,
                         const janus_decode_options* opt, const janus_decode_rows* rows,
                         int32_t* tokens, int32_t* n_tokens, float* sum_logprob,
-                        float* no_speech_prob, void* stream, const DecodeSampling* smp);
+                        float* no_speech_prob, void* stream, const DecodeSampling* smp,
+                        const BeamMode* beam = nullptr);
 
 extern "C" int janus_whisper_decode_greedy_ex(janus_whisper* w, const uint16_t* enc, int batch,
                                               const janus_decode_options* opt,
@@ -1249,6 +1300,47 @@ extern "C" int janus_whisper_decode_sample_rows_ex(janus_whisper* w, const uint1
   const DecodeSampling smp{1.0f, seeds, temperatures};
   return decode_entry(w, enc, batch, opt, rows, tokens, n_tokens, sum_logprob, no_speech_prob, stream,
                       &smp);
+}
+
+extern "C" int janus_whisper_decode_beam_ex(janus_whisper* w, const uint16_t* enc, int n_windows,
+                                            const janus_decode_options* opt, const janus_decode_rows* rows,
+                                            int beam_size, float length_penalty, int32_t* tokens,
+                                            int32_t* n_tokens, float* sum_logprob, float* no_speech_prob,
+                                            void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(w && enc && opt && tokens && n_tokens && sum_logprob, "null argument");
+    JANUS_CHECK(n_windows >= 1, "decode_beam: n_windows must be >= 1");
+    JANUS_CHECK(beam_size >= 1 && beam_size <= kBeamMax, "decode_beam: beam_size must be 1 .. 8");
+    JANUS_CHECK(length_penalty > 0.f, "decode_beam: length_penalty must be > 0");
+    JANUS_CHECK((int64_t)n_windows * beam_size <= kSkinnyMaxRows,
+                "decode_beam: windows x beam_size must be <= 512 rows");
+    JANUS_CHECK(!(rows && rows->pos_offset), "decode_beam: staggered rows (pos_offset) are not supported");
+    JANUS_CHECK(!(rows && rows->enc_index), "decode_beam: enc_index is built by the call (one encoder row per window)");
+    const int k = beam_size, B = n_windows * k;
+    // the window's prompt on each of its k rows, all of them on the window's encoder row
+    const bool per_row = rows && rows->prompts;
+    JANUS_CHECK(per_row || (opt->prompt && opt->prompt_len >= 1), "decode: missing prompt");
+    JANUS_CHECK(!per_row || (rows->prompt_lens && rows->stride >= 1), "decode: per-row prompts need lengths and a stride");
+    const int stride = per_row ? rows->stride : opt->prompt_len;
+    std::vector<int32_t> prompts((size_t)B * stride, 0), plens(B), eidx(B);
+    for (int b = 0; b < B; ++b) {
+      const int wi = b / k;
+      eidx[b] = wi;
+      plens[b] = per_row ? rows->prompt_lens[wi] : opt->prompt_len;
+      JANUS_CHECK(plens[b] >= 1 && plens[b] <= stride, "decode: per-row prompt length out of range");
+      const int32_t* src = per_row ? rows->prompts + (size_t)wi * stride : opt->prompt;
+      std::copy(src, src + plens[b], prompts.begin() + (size_t)b * stride);
+    }
+    janus_decode_rows br{};
+    br.prompts = prompts.data(); br.prompt_lens = plens.data(); br.stride = stride;
+    br.no_speech_token = rows ? rows->no_speech_token : -1;
+    br.enc_index = eidx.data(); br.n_enc = n_windows;
+    const BeamMode bm{k, length_penalty};
+    // (shared encoder rows: one lane; a null stream gets the lane's own, as every decode)
+    const int rc = decode_entry(w, enc, B, opt, &br, tokens, n_tokens, sum_logprob, no_speech_prob, stream,
+                                nullptr, &bm);
+    JANUS_CHECK(rc == 0, janus_last_error());
+  });
 }
 
 extern "C" int janus_whisper_decode_stand_slot(janus_whisper* w, int slot, int32_t* stand, int batch) {
@@ -1297,7 +1389,8 @@ extern "C" int janus_whisper_decode_path(janus_whisper* w, int32_t* enc_rows, in
 static int decode_entry(janus_whisper* w, const uint16_t* enc, int batch,
                         const janus_decode_options* opt, const janus_decode_rows* rows,
                         int32_t* tokens, int32_t* n_tokens, float* sum_logprob,
-                        float* no_speech_prob, void* stream, const DecodeSampling* smp) {
+                        float* no_speech_prob, void* stream, const DecodeSampling* smp,
+                        const BeamMode* beam) {
   return guarded([&] {
     JANUS_CHECK(w && enc && opt && tokens && n_tokens && sum_logprob, "null argument");
     JANUS_CHECK(batch >= 1, "decode: batch must be >= 1");
@@ -1327,7 +1420,7 @@ static int decode_entry(janus_whisper* w, const uint16_t* enc, int batch,
     if (nlanes == 1 && (s != nullptr || slot > 0)) {
       JANUS_CHECK(s != nullptr, "decode: a state slot > 0 needs a non-null stream");
       decode_greedy(w, *w->lanes[slot], e, batch, opt, rows, tokens, n_tokens, sum_logprob,
-                    no_speech_prob, s, nullptr, smp);
+                    no_speech_prob, s, nullptr, smp, beam);
       return;
     }
     // the null stream cannot be captured, and lanes run concurrently: each lane gets its
@@ -1390,7 +1483,7 @@ static int decode_entry(janus_whisper* w, const uint16_t* enc, int batch,
         decode_greedy(w, Z, e + (int64_t)b0 * w->cfg.n_audio_ctx * w->cfg.d_model, b1 - b0, opt,
                       rows ? &sub : nullptr, tokens + (int64_t)b0 * maxlen, n_tokens + b0,
                       sum_logprob + b0, no_speech_prob ? no_speech_prob + b0 : nullptr, Z.stream,
-                      nlanes > 1 ? &latch : nullptr, smp ? &ssub : nullptr);
+                      nlanes > 1 ? &latch : nullptr, smp ? &ssub : nullptr, beam);
       } catch (const std::exception& ex) {
         errs[i] = ex.what();
       } catch (...) {

@@ -53,7 +53,7 @@ import torch
 from .. import _native as nat
 from ..common import wavio
 from ..tokenizer import SOT_PREV
-from ..whisper import CONFIGS, WhisperEngine, shared_rows_in_place
+from ..whisper import CONFIGS, WhisperEngine, check_beam_args, shared_rows_in_place
 
 WINDOW_16K = 480000
 N_FRAMES = 3000          # log-mel frames per window (hop 160 @ 16 kHz)
@@ -411,7 +411,7 @@ def gather_windows(items, n_frames: int = N_FRAMES, device=None):
 
 def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_length: int = 448,
                       temperatures=TEMPERATURES, best_of: int = BEST_OF, utt_keys=None,
-                      speculative: bool = False):
+                      speculative: bool = False, beam_size: int = 1, length_penalty: float = 1.0):
     """faster-whisper's seek loop for several 16 kHz utterances at once: every round
     decodes the current window of each unfinished utterance as one GPU batch (per-row
     prompts), then the temperature fallback of the windows whose gates failed
@@ -423,7 +423,16 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     temperatures exactly as the sequential fallback does — the same results for one decode
     call's latency instead of up to len(temperatures) in a row, at (1 + 5 x 5) rows per
     window (the streaming encoder's setting: a few phrases at a time, latency-bound).
+    ``beam_size`` > 1 (up to 8; ``length_penalty`` > 0): the T = 0 decode of every window is
+    the beam decode (engine.decode_beam, windows chunked so that windows x beam_size stays
+    within one decode call's rows), as in faster-whisper; the fallback temperatures stay the
+    sampled best_of decodes and the gates read the winner's sum_logprob / (n + 1). The
+    speculative one-call form is greedy only.
     Returns one _Stream (segments + gate counters) per utterance."""
+    check_beam_args(beam_size, length_penalty)
+    if beam_size > 1 and speculative:
+        raise NotImplementedError("speculative=True decodes greedily in one call; beam_size > 1 "
+                                  "needs speculative=False")
     temperatures = tuple(float(t) for t in temperatures)
     if not temperatures or temperatures[0] != 0.0:
         raise NotImplementedError("the first temperature must be 0 (faster-whisper's default)")
@@ -444,6 +453,9 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     if spec:
         # the same in-place-or-gather row cap as the sequential fallback (_fallback)
         max_batch = max(1, min(max_batch, fallback_rows(engine) // per_row))
+    if beam_size > 1:
+        # a window's beams are rows of one decode call, capped like the sampled hypotheses
+        max_batch = max(1, min(max_batch, fallback_rows(engine) // beam_size))
     while True:
         act = [i for i, s in enumerate(streams) if s.active]
         if not act:
@@ -475,7 +487,11 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
                          for ti in range(1, len(temperatures))] for j in range(len(grp))]
                 n_tok = out.n_tokens.cpu().numpy()[0::per_row]
             else:
-                out = engine.decode_ex(enc, prompts=prompts, max_length=max_length)
+                if beam_size > 1:
+                    out = engine.decode_beam(enc, prompts=prompts, beam_size=beam_size,
+                                             length_penalty=length_penalty, max_length=max_length)
+                else:
+                    out = engine.decode_ex(enc, prompts=prompts, max_length=max_length)
                 t0 = out.rows()
                 n_tok = out.n_tokens.cpu().numpy()
             first, final, ndec = settle_round(engine, tk, t0, prompts, keys, enc, max_length,
@@ -518,16 +534,20 @@ class WhisperModel:
         self.stats = {"windows": 0, "needs_fallback": 0, "no_speech_skips": 0, "fallback_decodes": 0}
 
     def transcribe(self, audio, beam_size: int = 1, language: str = "en",
-                   temperature=TEMPERATURES, best_of: int = BEST_OF, **_ignored):
-        if beam_size != 1:
-            raise NotImplementedError("janus_amd decodes greedily (beam_size=1, transcriber.py:55)")
+                   temperature=TEMPERATURES, best_of: int = BEST_OF, length_penalty: float = 1.0,
+                   patience: float = 1, max_length: int = 448, **_ignored):
+        """faster-whisper's transcribe: ``beam_size`` 1 (greedy, the reference's call) .. 8
+        (beam search at T = 0, DESIGN.md §5k), ``length_penalty`` > 0, ``patience`` 1;
+        ``max_length``: the decoder's token limit per window (448)."""
+        check_beam_args(beam_size, length_penalty, patience)
         if language not in (None, "en"):
             raise NotImplementedError("*.en models transcribe English only (transcriber.py:56)")
         if isinstance(audio, str):
             audio = read_wav_16k(audio)
         audio = np.ascontiguousarray(audio, dtype=np.float32)
         temps = (float(temperature),) if np.isscalar(temperature) else tuple(temperature)
-        st = generate_segments(self.engine, [audio], temperatures=temps, best_of=best_of)[0]
+        st = generate_segments(self.engine, [audio], max_length=max_length, temperatures=temps,
+                               best_of=best_of, beam_size=beam_size, length_penalty=length_penalty)[0]
         self._count(st)
         info = TranscriptionInfo("en", 1.0, len(audio) / 16000.0)
         return iter(st.segments), info

@@ -262,6 +262,24 @@ def checkpoint_layers(W: dict, side: str) -> int:
 
 
 # --------------------------------------------------------------------- engine
+BEAM_MAX = 8           # largest beam_size (csrc/decoder.h kBeamMax)
+BEAM_MAX_ROWS = 512    # windows x beam_size of one beam decode (kSkinnyMaxRows)
+
+
+def check_beam_args(beam_size, length_penalty=1.0, patience=1):
+    """faster-whisper's beam options as this build runs them: beam_size 1 .. 8, patience 1,
+    length_penalty > 0. NotImplementedError for a value faster-whisper accepts and this build
+    does not run, ValueError for one that is no beam search at all."""
+    if isinstance(beam_size, bool) or not isinstance(beam_size, (int, np.integer)) or beam_size < 1:
+        raise ValueError(f"beam_size must be an integer >= 1, not {beam_size!r}")
+    if beam_size > BEAM_MAX:
+        raise NotImplementedError(f"beam_size {beam_size}: this build runs beam_size 1 .. {BEAM_MAX}")
+    if patience is not None and float(patience) != 1.0:
+        raise NotImplementedError(f"patience {patience!r}: this build runs patience 1 only")
+    if not float(length_penalty) > 0:
+        raise ValueError(f"length_penalty must be > 0, not {length_penalty!r}")
+
+
 # compute types of the encoder's linear layers (janus.h JANUS_ENC_COMPUTE_*)
 ENCODER_COMPUTE = {"float16": 0, "int8": 1}
 
@@ -487,6 +505,61 @@ class WhisperEngine:
                      ctypes.addressof(rows), tokens.data_ptr(), ntok.data_ptr(), slp.data_ptr(),
                      nsp.data_ptr(), nat.stream_ptr())
         del keep, pr, ei, po, row_t
+        return DecodeOut(tokens, ntok, slp, nsp, plens)
+
+    def decode_beam(self, enc: torch.Tensor, prompts=None, beam_size: int = 5,
+                    length_penalty: float = 1.0, max_length: int = 448, check_every: int = 16,
+                    timestamps: bool = True, xattn_splits: int = 0, cu_count: int = 0,
+                    temperature: float = 0.0, pos_offset=None, state_slot: int = 0,
+                    logits_blocks: int = 0, msplit_rows_n: int = 0, persistent: int = 0,
+                    path_flags: int = 0):
+        """janus_whisper_decode_beam_ex: beam search at temperature 0 over ``enc``
+        [windows][1500][d] (``prompts``: one token list per window; None = the SOT sequence).
+        Returns a DecodeOut with one row per window: the winning hypothesis' tokens,
+        ``n_tokens``, ``sum_logprob`` (its cumulative score S) and the window's
+        no_speech_prob. The rule (include/janus.h): per window up to
+        ``beam_size`` (1 .. 8) live beams, the best 2k candidates S + log-prob per step walked
+        in order (an <|endoftext|> candidate finishes a hypothesis, the others become the next
+        beams), the window stops at beam_size finished hypotheses or at ``max_length``, the
+        best S / n^length_penalty wins; patience 1. beam_size 1 is the greedy decode.
+        windows x beam_size <= 512; staggered rows (``pos_offset``) and ``temperature`` > 0
+        are rejected, a ``persistent`` request runs the launch path (decode_path())."""
+        check_beam_args(beam_size, length_penalty)
+        if pos_offset is not None:
+            raise ValueError("decode_beam: staggered rows (pos_offset) are not supported")
+        if not np.isscalar(temperature) or temperature > 0:
+            raise ValueError("decode_beam: beam search runs at temperature 0 (the fallback "
+                             "temperatures are sampled best_of decodes)")
+        W = int(enc.shape[0])
+        if W * beam_size > BEAM_MAX_ROWS:
+            raise ValueError(f"decode_beam: windows x beam_size = {W * beam_size} rows, the limit "
+                             f"is {BEAM_MAX_ROWS}")
+        opt, keep = self.decode_options(max_length, check_every, timestamps, xattn_splits, cu_count,
+                                        state_slot, logits_blocks, msplit_rows_n, persistent,
+                                        path_flags)
+        rows = janus_decode_rows()
+        rows.no_speech_token = tok.NO_SPEECH
+        plens = np.full(W, len(self.tokenizer.sot_sequence), np.int32)
+        pr = None
+        if prompts is not None:
+            if len(prompts) != W:
+                raise ValueError("decode_beam: one prompt per window")
+            plens = np.array([len(p) for p in prompts], np.int32)
+            stride = int(max(plens.max(), 1))
+            pr = np.zeros((W, stride), np.int32)
+            for b, p in enumerate(prompts):
+                pr[b, :len(p)] = p
+            rows.prompts = pr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            rows.prompt_lens = plens.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            rows.stride = stride
+        tokens = torch.empty(W, max_length, dtype=torch.int32, device=self.device)
+        ntok = torch.empty(W, dtype=torch.int32, device=self.device)
+        slp = torch.empty(W, dtype=torch.float32, device=self.device)
+        nsp = torch.empty(W, dtype=torch.float32, device=self.device)
+        nat.call("janus_whisper_decode_beam_ex", self._h, enc.data_ptr(), W, ctypes.addressof(opt),
+                 ctypes.addressof(rows), int(beam_size), ctypes.c_float(length_penalty),
+                 tokens.data_ptr(), ntok.data_ptr(), slp.data_ptr(), nsp.data_ptr(), nat.stream_ptr())
+        del keep, pr
         return DecodeOut(tokens, ntok, slp, nsp, plens)
 
     def decode_stand(self, batch: int, state_slot: int = 0):
