@@ -11,6 +11,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include "janus.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -232,6 +233,28 @@ int janus_beam_step(const void* parts, const void* tops, int nblk, int eot, int 
 int janus_beam_reorder_f16(uint16_t* kc, uint16_t* vc, int layers, int n_windows, int beam_size,
                            int n_ctx, int d, int pos, const int32_t* parent, const int32_t* moved,
                            void* stream);
+
+/*
+ * Test-only view of the decode planner (csrc/decode_plan.h): the plan a decode call with
+ * these arguments gets on a lane of `cus` CUs, without an engine or a device. `resident`
+ * answers whether the persistent segments' grid is co-resident (the library asks the
+ * device's occupancy; the two-blocks-per-CU grid of JANUS_DEC_PATH_SEG_2CU, which asks it
+ * too, is described as the one-block-per-CU grid); multi_lane: the call is one lane of
+ * several. temperature > 0 samples, temperatures [host] float [batch] (nullable) are per-row
+ * temperatures, beam_size > 0 is a beam search over rows laid out as
+ * janus_whisper_decode_beam_ex builds them. stand [host] int32 [n_stand] / stand_maxlen
+ * (nullable / 0): where the lane's row slots stand for a staggered call.
+ * text [text_cap]: the plan as name=value lines (fields only the code around the positions
+ * reads as call.name), then pairs= and groups= as comma-separated integers (pairs: b0, b1,
+ * e per pair; groups: 8 per group), NUL-terminated. key [key_cap]: the plan's contribution
+ * to the graph cache key, *n_key values. A call the planner rejects, or a buffer too small,
+ * returns non-zero with janus_last_error.
+ */
+int janus_decode_plan_describe(const janus_whisper_config* cfg, const janus_decode_options* opt,
+                               const janus_decode_rows* rows, int batch, int cus, int resident,
+                               int multi_lane, float temperature, const float* temperatures,
+                               int beam_size, const int32_t* stand, int n_stand, int stand_maxlen,
+                               char* text, int text_cap, int64_t* key, int key_cap, int32_t* n_key);
 
 #ifdef __cplusplus
 }

@@ -127,6 +127,9 @@ SIGNATURES = {
     "janus_beam_step": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P,
                         _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "janus_beam_reorder_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
+    # test-only view of the decode planner (no engine, no device)
+    "janus_decode_plan_describe": [_P, _P, _P, _I32, _I32, _I32, _I32, _F32, _P, _I32, _P, _I32, _I32,
+                                   _P, _I32, _P, _I32, _P],
 }
 RESTYPES = {"janus_conv1d_packed_size": ctypes.c_int64}
 

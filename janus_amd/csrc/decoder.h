@@ -1,20 +1,9 @@
 // Decoder-loop kernels (decoder.hip).
 #pragma once
 #include "common.h"
+#include "decode_shapes.h"  // DecodeRules, kBeamMax
 
 namespace janus {
-
-struct DecodeRules {
-  int eot;
-  int suppress_blank, blank;     // SuppressBlank at the first sampled token
-  int ts_begin;                  // first timestamp token id; -1 disables timestamp rules
-  int no_timestamps;             // <|notimestamps|> (always suppressed in timestamp mode)
-  int max_initial_ts;            // max_initial_timestamp index (-1: none)
-  int target;                    // token whose raw softmax probability is tracked (no-speech), -1: none
-  float inv_temp;                // 0: greedy (argmax); > 0: sample at temperature 1 / inv_temp
-                                 // (Gumbel-max over the rule-filtered logits, noise from
-                                 // sample_noise(seed of the row, position, token))
-};
 
 // Per-row rule state carried across steps (computed by the selector for the next step).
 struct RowRules {
@@ -43,8 +32,7 @@ struct LogitPart {
 // beside its LogitPart, sorted (logit descending, first index on ties); unused slots hold
 // (-inf, 0x7fffffff). Two sets, because which applies is known only once the whole row's
 // timestamp-mass rule is evaluated: every allowed token / the allowed timestamps.
-constexpr int kBeamTop = 16;    // 2 * the largest beam size
-constexpr int kBeamMax = 8;
+constexpr int kBeamTop = 16;    // 2 * the largest beam size (kBeamMax)
 struct BeamTop {
   float av[kBeamTop]; int ai[kBeamTop];
   float tv[kBeamTop]; int ti[kBeamTop];

@@ -1,6 +1,11 @@
 // Kernel-level C-ABI (include/janus_kernels.h): thin wrappers over the launchers.
+#include <algorithm>
+#include <cstring>
+#include <vector>
 #include "kernels.h"
 #include "decoder.h"
+#include "dec_persist.h"
+#include "decode_plan.h"
 #include "../../include/janus_kernels.h"
 
 namespace janus {
@@ -304,5 +309,33 @@ extern "C" int janus_beam_reorder_f16(uint16_t* kc, uint16_t* vc, int layers, in
     JANUS_CHECK(kc && vc && parent && moved, "null argument");
     beam_reorder_launch(reinterpret_cast<_Float16*>(kc), reinterpret_cast<_Float16*>(vc), layers, n_windows,
                         beam_size, n_ctx, d, pos, parent, moved, (hipStream_t)stream);
+  });
+}
+
+extern "C" int janus_decode_plan_describe(const janus_whisper_config* cfg, const janus_decode_options* opt,
+                                          const janus_decode_rows* rows, int batch, int cus, int resident,
+                                          int multi_lane, float temperature, const float* temperatures,
+                                          int beam_size, const int32_t* stand, int n_stand, int stand_maxlen,
+                                          char* text, int text_cap, int64_t* key, int key_cap, int32_t* n_key) {
+  return guarded([&] {
+    JANUS_CHECK(cfg && opt && text && key && n_key, "null argument");
+    JANUS_CHECK(batch >= 1, "decode: batch must be >= 1");
+    const std::vector<uint32_t> seeds(batch, 0);
+    const DecodeSampling smp{temperatures ? 1.0f : temperature, seeds.data(), temperatures};
+    const BeamMode bm{beam_size, 1.0f};
+    const std::vector<int32_t> st(stand, stand + (stand ? n_stand : 0));
+    SegDevice seg;
+    seg.grid = [](int B, int n_cus, bool) { return dec_seg_grid(B, n_cus, false); };
+    seg.resident = [resident](int, int) { return resident != 0; };
+    const DecodePlan P = plan_decode(*cfg, *opt, rows, (temperatures || temperature > 0.f) ? &smp : nullptr,
+                                     beam_size > 0 ? &bm : nullptr, batch, cus, multi_lane != 0,
+                                     LaneStand{&st, stand_maxlen}, seg);
+    const std::string d = P.describe();
+    std::vector<int64_t> k;
+    P.append_key(k);
+    JANUS_CHECK((int)d.size() < text_cap && (int)k.size() <= key_cap, "decode_plan_describe: buffer too small");
+    std::memcpy(text, d.c_str(), d.size() + 1);
+    std::copy(k.begin(), k.end(), key);
+    *n_key = (int32_t)k.size();
   });
 }

@@ -1,14 +1,12 @@
-// Launcher declarations shared by the host-side orchestration (whisper.cpp, vocoder.cpp).
+// Launcher declarations shared by the host-side orchestration (whisper.cpp, decode.cpp, vocoder.cpp).
 #pragma once
 #include "common.h"
+#include "decode_shapes.h"  // kSkinnyMaxRows
 
 namespace janus {
 
 // ------------------------------------------------------------------ GEMM
 enum GemmEpi { EPI_F16 = 0, EPI_GELU_F16 = 1, EPI_RESID_F32 = 2, EPI_F32 = 3, EPI_QKV = 4 };
-// Largest M the skinny (decoder-step) GEMM takes: a decode batch of 64 windows x 5 sampled
-// hypotheses (faster-whisper's best_of) is 320 rows.
-constexpr int kSkinnyMaxRows = 512;
 
 struct GemmArgs {
   const _Float16* A; int64_t lda;  // [M][K]

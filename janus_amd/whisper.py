@@ -613,7 +613,7 @@ class DecodePath:
 
 def shared_rows_in_place(cfg) -> bool:
     """True when decoder rows sharing an encoder row (enc_index) read it in place by default
-    on this model: PAIR blocks up to 8 heads / d_model 512 (whisper.cpp pair_ok). Otherwise a
+    on this model: PAIR blocks up to 8 heads / d_model 512 (decode_plan.cpp pair_ok). Otherwise a
     call gathers one encoder copy per row — the 768-wide 12-head family too, whose in-place
     blocks (DEC_PATH_XROWS) measured slower than the copies — and callers keep their
     sampled batches small (services/transcriber.py FALLBACK_ROWS_GATHER)."""

@@ -653,3 +653,37 @@ def test_persistent_staggered_bit_identical(base_engine, gpu, rows, mode, flags)
         for j in range(rows):
             k = plen + int(n[j])
             assert torch.equal(t[j, :k], rt[j, :k]), (bi, j)
+
+
+@pytest.fixture(scope="module")
+def launch_engines(engine, base_engine, gpu):
+    """The engines of tests/decode_launches.py's models: the module's tiny.en and base.en
+    ones, the small-cut one (768 wide, 12 heads) made on first use."""
+    import decode_launches as dl
+    made = {"tiny": engine[0], "base": base_engine[0]}
+
+    def get(model):
+        if model not in made:
+            made[model] = dl.make_engine(model)
+        return made[model]
+    return get
+
+
+def _launch_case_ids():
+    import decode_launches as dl
+    return [n for n in dl.CASES if n != "stagger_continued"]
+
+
+@pytest.mark.parametrize("name", _launch_case_ids())
+def test_decode_launch_counts(launch_engines, name):
+    """The launch structure of a decode call is the plan's alone: positions stepped, kernel
+    launches issued (captured graph nodes), how the rows reached their encoder output and the
+    persistent level run equal tests/golden/decode_launches.json, recorded by
+    tests/golden/make_decode_launches.py before the decode call's host side was split up
+    (the staggered pair: a fresh call, then the call that continues two of its rows)."""
+    import decode_launches as dl
+    golden = dl.golden()
+    for case in ([name, "stagger_continued"] if name == "stagger_fresh" else [name]):
+        got = dl.run_case(launch_engines(dl.CASES[case][0]), case)
+        print(case, got, golden[case])
+        assert got == golden[case], case
