@@ -499,6 +499,71 @@ int janus_whisper_decode_stand(janus_whisper* w, int32_t* stand, int batch);
 int janus_whisper_decode_check(janus_whisper* w, int slot);
 int janus_whisper_decode_stand_slot(janus_whisper* w, int slot, int32_t* stand, int batch);
 
+/*
+ * Word-level timestamps: the alignment pass behind faster-whisper's
+ * transcribe(word_timestamps=True) (WhisperModel.find_alignment -> CTranslate2
+ * Whisper.align; transcriber.py:53-57 with that option). CTranslate2's align cannot be pinned
+ * offline; the rule built here, per window, from the window's encoder output enc [1500][d],
+ * its content size `size` in mel frames and its text tokens `text` (ids < eot, all the
+ * window's segments concatenated, len(text) >= 1):
+ *  1. seq = sot_sequence + [<|notimestamps|>] + text + [eot], n tokens. The decoder runs over
+ *     seq teacher-forced (causal self-attention, cross-attention over all 1500 frames), fp16
+ *     weights, fp32 accumulation.
+ *  2. Alignment heads: every head of the last half of the decoder layers (l >= dec_layers / 2;
+ *     CTranslate2's default for a checkpoint that names none) unless
+ *     janus_whisper_set_alignment_heads named others.
+ *  3. Per alignment head, P[h][i][t] = softmax over all 1500 frames of row i's scaled
+ *     cross-attention scores. Frames t < F = size / 2 are kept; per head and frame the n rows
+ *     are normalised, (P - mean) / std with the population standard deviation; a median
+ *     filter of width 7 runs along the frames with reflect padding by 3 (F <= 3: no filter);
+ *     the heads are averaged; rows len(sot_sequence) .. n - 2 are kept: A [N][F],
+ *     N = len(text) + 1, row r being the step that predicts (text + [eot])[r].
+ *  4. DTW on x = -A, fp32, OpenAI's formulation: cost[0][0] = 0, the rest of the border +inf;
+ *     cost[i][j] = x[i-1][j-1] + min(c0 = cost[i-1][j-1], c1 = cost[i-1][j], c2 = cost[i][j-1]);
+ *     trace = 0 if c0 < c1 and c0 < c2, else 1 if c1 < c0 and c1 < c2, else 2. Backtrace from
+ *     (N, F) with trace[0][*] = 2 and trace[*][0] = 1: 0 moves to (i-1, j-1), 1 to (i-1, j),
+ *     2 to (i, j-1); (i-1, j-1) is emitted before each move and the list reversed:
+ *     text_indices / time_indices of length L <= N + F. The additions and comparisons run in
+ *     exactly this order, so the path of a given matrix is exact, ties included.
+ *  5. token_probs[r] = softmax over ids [0, eot) of the logits of row len(sot_sequence) + r,
+ *     taken at text[r], r < len(text).
+ * Words, their times (time_indices * 0.02 s at the jumps of text_indices) and faster-whisper's
+ * add_word_timestamps / seek rules are host code: janus_amd/services/transcriber.py,
+ * DESIGN.md §5l.
+ *
+ * janus_whisper_align, several windows of different lengths in one call:
+ *   enc            [device] fp16 [n_enc][1500][d]
+ *   tokens         [host] int32 [n_windows][stride]: window w's seq in its first token_lens[w]
+ *                  entries; token_lens [host] int32 [n_windows], sot_len + 3 <= n <= n_text_ctx
+ *   sizes          [host] int32 [n_windows], each in [2, 3000]
+ *   enc_index      [host] int32 [n_windows] (nullable: window w attends to enc row w), as
+ *                  janus_decode_rows.enc_index
+ *   sot_len, eot   len(sot_sequence) and the <|endoftext|> id
+ *   text_indices, time_indices [device] int32 [n_windows][path_stride] (-1 past a window's
+ *                  path; path_stride >= every window's N + F), path_lens [device] int32
+ *                  [n_windows]
+ *   token_probs    [device] f32 [n_windows][stride]: rule 5 in the first len(text) entries of
+ *                  each row, 0 after
+ *   attn_out       [device] f32, nullable: every window's A [N][F], the windows back to back
+ *   phases         0 = the whole call; a mask of 1 (decoder forward and token_probs), 2 (A
+ *                  from the kept probabilities) and 4 (DTW) runs those parts alone over what
+ *                  the previous call of the same shape left in the context's workspace
+ *                  (measurement only)
+ * The call allocates from the context's workspace, uses no decoder state slot (it may run
+ * between two staggered decode calls) and rejects (non-zero status) a sequence longer than
+ * n_text_ctx, a window without text, a size outside [2, 3000] or a token id out of range.
+ *
+ * janus_whisper_set_alignment_heads: pairs [host] int32 [n_pairs][2] = (layer, head),
+ * 1 .. 64 distinct pairs in range; pairs NULL with n_pairs 0 restores the default of rule 2.
+ */
+int janus_whisper_set_alignment_heads(janus_whisper* w, const int32_t* pairs, int n_pairs);
+int janus_whisper_align(janus_whisper* w, const uint16_t* enc, int n_enc, int n_windows,
+                        const int32_t* tokens, const int32_t* token_lens, int stride,
+                        const int32_t* sizes, const int32_t* enc_index, int sot_len, int eot,
+                        int32_t* text_indices, int32_t* time_indices, int32_t* path_lens,
+                        int path_stride, float* token_probs, float* attn_out, int phases,
+                        void* stream);
+
 /* ------------------------------------------------------------ vocoder --- */
 /*
  * Local Firefly-GAN decoder (fish-speech HiFiGANGenerator architecture) replacing the

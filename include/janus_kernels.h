@@ -256,6 +256,32 @@ int janus_decode_plan_describe(const janus_whisper_config* cfg, const janus_deco
                                int beam_size, const int32_t* stand, int n_stand, int stand_maxlen,
                                char* text, int text_cap, int64_t* key, int key_cap, int32_t* n_key);
 
+/*
+ * Word alignment kernels (janus_whisper_align), one test entry each. Device pointers.
+ *
+ * janus_align_dtw_f32: the DTW of janus.h's rule 4 on x f32 [N][F] as given (the alignment
+ * call passes -A): cost[i][j] = x[i-1][j-1] + min(c0, c1, c2) with the comparisons in that
+ * rule's order, so the path is exact for a given matrix, ties included. trace u8
+ * [N + 1][F + 1] (scratch; the border entries are not written), text_indices / time_indices
+ * int32 [N + F] (-1 past the path), path_len int32 [1]. N <= 511.
+ *
+ * janus_align_reduce_f32: probs f32 [heads][n][F] -> A f32 [n - sot_len - 1][F] (rule 3:
+ * (P - mean) / std over the n rows per head and frame, median of 7 along the frames with
+ * reflect padding unless F <= 3, mean over heads, rows sot_len .. n - 2).
+ *
+ * janus_align_token_prob_f16: prob[r] = softmax(LayerNorm(x[r]; gamma, beta, 1e-5) . W^T)
+ * [target[r]] over the V columns of W fp16 [V][d] (rule 5 with V = eot); x f32 [rows][d],
+ * target int32 [rows] in [0, V). The logits exist for one chunk of rows at a time.
+ * Each of the three waits for the stream before it returns.
+ */
+int janus_align_dtw_f32(const float* x, int N, int F, uint8_t* trace, int32_t* text_indices,
+                        int32_t* time_indices, int32_t* path_len, void* stream);
+int janus_align_reduce_f32(const float* probs, int heads, int n, int F, int sot_len, float* A,
+                           void* stream);
+int janus_align_token_prob_f16(const float* x, const float* gamma, const float* beta,
+                               const uint16_t* W, int rows, int d, int V, const int32_t* target,
+                               float* prob, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,9 @@ SIGNATURES = {
     "janus_whisper_decode_sample_ex": [_P, _P, _I32, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P],
     "janus_whisper_decode_sample_rows_ex": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "janus_whisper_decode_beam_ex": [_P, _P, _I32, _P, _P, _I32, _F32, _P, _P, _P, _P, _P],
+    "janus_whisper_set_alignment_heads": [_P, _P, _I32],
+    "janus_whisper_align": [_P, _P, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I32, _P, _P, _P, _I32, _P, _P,
+                            _I32, _P],
     "janus_whisper_decode_check": [_P, _I32],
     "janus_whisper_decode_info": [_P, _P, _P],
     "janus_whisper_decode_path": [_P, _P, _P],
@@ -127,6 +130,10 @@ SIGNATURES = {
     "janus_beam_step": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P,
                         _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "janus_beam_reorder_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
+    # word alignment kernels
+    "janus_align_dtw_f32": [_P, _I32, _I32, _P, _P, _P, _P, _P],
+    "janus_align_reduce_f32": [_P, _I32, _I32, _I32, _I32, _P, _P],
+    "janus_align_token_prob_f16": [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P],
     # test-only view of the decode planner (no engine, no device)
     "janus_decode_plan_describe": [_P, _P, _P, _I32, _I32, _I32, _I32, _F32, _P, _I32, _P, _I32, _I32,
                                    _P, _I32, _P, _I32, _P],

@@ -2,6 +2,8 @@
 #include <algorithm>
 #include <cstring>
 #include <vector>
+#include "align.h"
+#include "devmem.h"
 #include "kernels.h"
 #include "decoder.h"
 #include "dec_persist.h"
@@ -337,5 +339,76 @@ extern "C" int janus_decode_plan_describe(const janus_whisper_config* cfg, const
     std::memcpy(text, d.c_str(), d.size() + 1);
     std::copy(k.begin(), k.end(), key);
     *n_key = (int32_t)k.size();
+  });
+}
+
+// ------------------------------------------------------------------ word alignment kernels
+namespace {
+// a one-window device table for the alignment kernels' test entries
+const AlignWinDev* one_window(DevMem& m, int n, int F, int N, hipStream_t s) {
+  AlignWinDev W{};
+  W.n = n; W.F = F; W.N = N;
+  m.ensure(sizeof(W));
+  JANUS_HIP(hipMemcpyAsync(m.p, &W, sizeof(W), hipMemcpyHostToDevice, s));
+  JANUS_HIP(hipStreamSynchronize(s));   // W is a local
+  return m.as<AlignWinDev>();
+}
+}  // namespace
+
+extern "C" int janus_align_dtw_f32(const float* x, int N, int F, uint8_t* trace, int32_t* text_indices,
+                                   int32_t* time_indices, int32_t* path_len, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(x && trace && text_indices && time_indices && path_len, "null argument");
+    JANUS_CHECK(N >= 1 && N <= 511 && F >= 1 && F <= 4096, "align_dtw: 1 <= N <= 511, 1 <= F <= 4096");
+    hipStream_t s = (hipStream_t)stream;
+    DevMem win, rev;
+    rev.ensure(sizeof(int32_t) * 2 * (size_t)(N + F));
+    align_dtw_launch(x, one_window(win, N + 1, F, N, s), 1, 0, trace, rev.as<int32_t>(), text_indices,
+                     time_indices, path_len, N + F, s);
+    JANUS_HIP(hipStreamSynchronize(s));   // the scratch goes with this call
+  });
+}
+
+extern "C" int janus_align_reduce_f32(const float* probs, int heads, int n, int F, int sot_len, float* A,
+                                      void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(probs && A, "null argument");
+    JANUS_CHECK(heads >= 1 && heads <= kAlignMaxHeads && F >= 1 && F <= 4096 && sot_len >= 0 && n >= sot_len + 2 &&
+                    n <= 4096, "align_reduce: 1 .. 64 heads, 1 <= F <= 4096, sot_len + 2 <= n <= 4096");
+    hipStream_t s = (hipStream_t)stream;
+    DevMem win, stats;
+    stats.ensure(sizeof(double) * 2 * (size_t)heads * F);
+    align_reduce_launch(probs, one_window(win, n, F, n - sot_len - 1, s), 1, heads, sot_len, n, F,
+                        stats.as<double>(), A, s);
+    JANUS_HIP(hipStreamSynchronize(s));
+  });
+}
+
+extern "C" int janus_align_token_prob_f16(const float* x, const float* gamma, const float* beta,
+                                          const uint16_t* W, int rows, int d, int V, const int32_t* target,
+                                          float* prob, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(x && gamma && beta && W && target && prob, "null argument");
+    JANUS_CHECK(rows >= 1 && rows <= 4096 && d % 8 == 0 && V >= 1, "align_token_prob: 1 .. 4096 rows, d % 8 == 0");
+    hipStream_t s = (hipStream_t)stream;
+    const int vpad = (V + 7) & ~7, chunk = 64;
+    DevMem a, logits, idx;
+    a.ensure(sizeof(_Float16) * (size_t)rows * d);
+    logits.ensure(sizeof(float) * (size_t)chunk * vpad);
+    std::vector<int32_t> ident(rows);
+    for (int r = 0; r < rows; ++r) ident[r] = r;
+    idx.ensure(sizeof(int32_t) * rows);
+    JANUS_HIP(hipMemcpyAsync(idx.p, ident.data(), sizeof(int32_t) * rows, hipMemcpyHostToDevice, s));
+    layernorm_launch(x, gamma, beta, a.as<_Float16>(), rows, d, 1e-5f, s);
+    for (int r0 = 0; r0 < rows; r0 += chunk) {   // no [rows][V] logits: one chunk of rows at a time
+      const int m = std::min(chunk, rows - r0);
+      GemmArgs g;
+      g.A = a.as<_Float16>() + (int64_t)r0 * d; g.lda = d;
+      g.W = reinterpret_cast<const _Float16*>(W); g.ldw = d;
+      g.bias = nullptr; g.C = logits.p; g.ldc = vpad; g.R = nullptr; g.ldr = 0; g.M = m; g.N = V; g.K = d;
+      gemm_nt128_launch(EPI_F32, g, s);
+      align_rowprob_launch(logits.as<float>(), vpad, V, target + r0, idx.as<int32_t>() + r0, m, prob, s);
+    }
+    JANUS_HIP(hipStreamSynchronize(s));
   });
 }

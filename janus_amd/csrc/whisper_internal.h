@@ -5,6 +5,7 @@
 #include <memory>
 #include <mutex>
 #include <vector>
+#include "align.h"
 #include "devmem.h"
 #include "kernels.h"
 #include "../../include/janus.h"
@@ -92,6 +93,7 @@ struct janus_whisper {
   // decoder lanes: each owns the workspaces, captured graphs and stream of one batch slice
   std::vector<std::unique_ptr<janus::DecLane>> lanes;
   int last_slot = 0;  // state slot of the last decode call (decode_info reports it)
+  janus::AlignState align;  // word alignment (align_call.cpp): heads, plan and workspaces
   hipEvent_t ev_in = nullptr;
   ~janus_whisper() {
     if (ev_in) (void)hipEventDestroy(ev_in);

@@ -100,6 +100,15 @@ def fallback_seed(utt: int, window: int, temp_index: int, hyp: int) -> int:
 
 
 @dataclasses.dataclass
+class Word:
+    """faster-whisper's Word: times in seconds from the start of the audio."""
+    start: float
+    end: float
+    word: str
+    probability: float
+
+
+@dataclasses.dataclass
 class Segment:
     id: int
     seek: int
@@ -112,6 +121,7 @@ class Segment:
     compression_ratio: float
     no_speech_prob: float
     needs_fallback: bool = False   # the T = 0 decode failed its gates (fallback entered)
+    words: list = None             # [Word] with word_timestamps=True, else None
 
 
 @dataclasses.dataclass
@@ -244,6 +254,144 @@ def split_window(tk, tokens, seek, segment_size):
     return segs, nseek
 
 
+# --------------------------------------------------------------- word timestamps
+# faster-whisper 1.x find_alignment / merge_punctuations / add_word_timestamps over the
+# path and token probabilities of WhisperEngine.align (include/janus.h rules 1 - 5 on the
+# GPU; rules 6 - 8 here).
+PREPEND_PUNCTUATIONS = "\"'“¿([{-"
+APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
+SENTENCE_END_MARKS = ".。!！?？"
+
+
+def find_alignment(tk, text_tokens, alignment):
+    """One window's words from its alignment (faster-whisper find_alignment after the
+    CTranslate2 call): [dict(word, tokens, start, end, probability)], times in seconds from
+    the window's start. ``alignment``: WhisperEngine.align's result for ``text_tokens`` (its
+    text_indices / time_indices / token_probs); None or no text gives no words."""
+    if alignment is None or len(text_tokens) == 0:
+        return []
+    words, word_tokens = tk.split_to_word_tokens(list(text_tokens) + [tk.eot])
+    if len(word_tokens) <= 1:
+        return []
+    boundaries = np.pad(np.cumsum([len(t) for t in word_tokens[:-1]]), (1, 0))
+    if len(boundaries) <= 1:
+        return []
+    text_indices = np.asarray(alignment.text_indices)
+    time_indices = np.asarray(alignment.time_indices)
+    jumps = np.pad(np.diff(text_indices), (1, 0), constant_values=1).astype(bool)
+    jump_times = time_indices[jumps] * TIME_PRECISION
+    starts = jump_times[boundaries[:-1]]
+    ends = jump_times[boundaries[1:]]
+    probs = np.asarray(alignment.token_probs, np.float64)
+    return [dict(word=w, tokens=list(t), start=float(st), end=float(en),
+                 probability=float(np.mean(probs[i:j])))
+            for w, t, st, en, i, j in zip(words, word_tokens, starts, ends, boundaries[:-1], boundaries[1:])]
+
+
+def merge_punctuations(alignment, prepended=PREPEND_PUNCTUATIONS, appended=APPEND_PUNCTUATIONS):
+    """faster-whisper merge_punctuations, in place: a word that is a space plus a prepended
+    mark joins the word after it, an appended mark joins the word before it (unless that ends
+    in a space); the emptied entry keeps its times with word "" and no tokens."""
+    i, j = len(alignment) - 2, len(alignment) - 1
+    while i >= 0:
+        previous, following = alignment[i], alignment[j]
+        if previous["word"].startswith(" ") and previous["word"].strip() in prepended:
+            following["word"] = previous["word"] + following["word"]
+            following["tokens"] = previous["tokens"] + following["tokens"]
+            previous["word"] = ""
+            previous["tokens"] = []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(alignment):
+        previous, following = alignment[i], alignment[j]
+        if not previous["word"].endswith(" ") and following["word"] in appended:
+            previous["word"] = previous["word"] + following["word"]
+            previous["tokens"] = previous["tokens"] + following["tokens"]
+            following["word"] = ""
+            following["tokens"] = []
+        else:
+            i = j
+        j += 1
+
+
+def add_word_timestamps(tk, segments, alignment, seek, last_speech_timestamp,
+                        prepend_punctuations=PREPEND_PUNCTUATIONS,
+                        append_punctuations=APPEND_PUNCTUATIONS):
+    """faster-whisper add_word_timestamps over ONE window: ``segments`` its sub-segments as
+    dicts(start, end, tokens) (times absolute), updated in place with "words" ([dict(word,
+    start, end, probability)], absolute times rounded to 0.01 s) and the start / end the word
+    times move; ``alignment``: find_alignment's words of the window's concatenated text
+    tokens. Returns the new last_speech_timestamp."""
+    if not segments:
+        return last_speech_timestamp
+    per_segment = [[t for t in seg["tokens"] if t < tk.eot] for seg in segments]
+    durations = np.array([w["end"] - w["start"] for w in alignment])
+    durations = durations[durations.nonzero()]
+    median_duration = min(0.7, float(np.median(durations))) if len(durations) > 0 else 0.0
+    max_duration = median_duration * 2
+    if len(durations) > 0:       # truncate long words at sentence boundaries
+        for i in range(1, len(alignment)):
+            if alignment[i]["end"] - alignment[i]["start"] > max_duration:
+                if alignment[i]["word"] in SENTENCE_END_MARKS:
+                    alignment[i]["end"] = alignment[i]["start"] + max_duration
+                elif alignment[i - 1]["word"] in SENTENCE_END_MARKS:
+                    alignment[i]["start"] = alignment[i]["end"] - max_duration
+    merge_punctuations(alignment, prepend_punctuations, append_punctuations)
+    time_offset = seek * 0.01
+    word_index = 0
+    for seg, seg_tokens in zip(segments, per_segment):
+        saved, words = 0, []
+        while word_index < len(alignment) and saved < len(seg_tokens):
+            timing = alignment[word_index]
+            if timing["word"]:
+                words.append(dict(word=timing["word"], start=round(time_offset + timing["start"], 2),
+                                  end=round(time_offset + timing["end"], 2),
+                                  probability=timing["probability"]))
+            saved += len(timing["tokens"])
+            word_index += 1
+        if words:
+            # the first and second word after a pause: at most twice the median duration
+            if words[0]["end"] - last_speech_timestamp > median_duration * 4 and (
+                    words[0]["end"] - words[0]["start"] > max_duration
+                    or (len(words) > 1 and words[1]["end"] - words[0]["start"] > max_duration * 2)):
+                if len(words) > 1 and words[1]["end"] - words[1]["start"] > max_duration:
+                    boundary = max(words[1]["end"] / 2, words[1]["end"] - max_duration)
+                    words[0]["end"] = words[1]["start"] = boundary
+                words[0]["start"] = max(0, words[0]["end"] - max_duration)
+            # prefer the segment-level start / end when the first / last word is too long
+            if seg["start"] < words[0]["end"] and seg["start"] - 0.5 > words[0]["start"]:
+                words[0]["start"] = max(0, min(words[0]["end"] - median_duration, seg["start"]))
+            else:
+                seg["start"] = words[0]["start"]
+            if seg["end"] > words[-1]["start"] and seg["end"] + 0.5 < words[-1]["end"]:
+                words[-1]["end"] = max(words[-1]["start"] + median_duration, seg["end"])
+            else:
+                seg["end"] = words[-1]["end"]
+            last_speech_timestamp = seg["end"]
+        seg["words"] = words
+    return last_speech_timestamp
+
+
+def word_seek(segments, seek, nseek, single_timestamp_ending):
+    """Rule 8: with word timestamps, a window that does not end in a single timestamp moves
+    the next seek to the end of its last word, when that lies after the window's start."""
+    if single_timestamp_ending:
+        return nseek
+    ends = [w["end"] for seg in segments for w in seg.get("words", [])]
+    if ends and ends[-1] > seek * 0.01:
+        return round(ends[-1] * 100)
+    return nseek
+
+
+def window_text_tokens(tk, tokens, seek, size):
+    """The text tokens (< eot) a window's alignment runs over: those of all its sub-segments
+    (split_window), concatenated."""
+    segs, _ = split_window(tk, list(tokens), seek, size)
+    return [t for (_, _, part) in segs for t in part if t < tk.eot]
+
+
 class _Stream:
     """generate_segments state of one utterance."""
 
@@ -259,6 +407,9 @@ class _Stream:
         self.window_tokens = []        # the settled tokens of every window, in order
         self.window_rows = []          # every window's T = 0 decode: (tokens, avg_logprob, nsp)
         self.sampled = 0               # tokens sampled at T = 0 over every window (incl. eot)
+        self.last_speech_timestamp = 0.0   # word timestamps: the end of the last segment with words
+        self.window_seeks = []         # (seek, size, next seek) of every window, in order
+        self.window_alignments = []    # word timestamps: every window's Alignment (None: none run)
 
     def transcript(self):
         """transcribe_buffer's join of the segments (transcriber.py:59-64)."""
@@ -343,11 +494,14 @@ def settle_round(engine, tk, rows, prompts, keys, enc, max_length, temperatures=
     return first, final, ndec
 
 
-def advance(tk, s, size, c0, r, nd, sampled: int = 0):
+def advance(tk, s, size, c0, r, nd, sampled: int = 0, word_timestamps: bool = False, alignment=None,
+            prepend_punctuations=PREPEND_PUNCTUATIONS, append_punctuations=APPEND_PUNCTUATIONS):
     """generate_segments' update of one utterance after its window [seek, seek + size) settled
     (c0: the T = 0 Candidate, r: the settled one, nd: sampled re-decodes, sampled: tokens the
     T = 0 decode emitted): the counters, the no-speech skip, the segments (start == end or
-    blank text dropped), the next seek and the prompt reset."""
+    blank text dropped), the next seek and the prompt reset. ``word_timestamps``: the
+    window's sub-segments get their words from ``alignment`` (WhisperEngine.align over
+    window_text_tokens) before they are filtered, and the seek follows rule 8."""
     s.windows += 1
     s.fallbacks += int(c0.needs_fallback)
     s.fallback_decodes += nd
@@ -357,17 +511,34 @@ def advance(tk, s, size, c0, r, nd, sampled: int = 0):
     # no-speech skip on the settled result (generate_segments after the fallback)
     if r.no_speech_prob > NO_SPEECH_THRESHOLD and not r.avg_logprob > LOG_PROB_THRESHOLD:
         s.skips += 1
+        s.window_seeks.append((s.seek, size, s.seek + size))
+        if word_timestamps:
+            s.window_alignments.append(None)
         s.seek += size
         return
     segs, nseek = split_window(tk, r.tokens, s.seek, size)
-    for (st, en, part) in segs:
+    words = [None] * len(segs)
+    if word_timestamps:
+        toks = r.tokens
+        single = len(toks) >= 2 and toks[-2] < tk.timestamp_begin <= toks[-1]
+        cur = [dict(start=st, end=en, tokens=part) for (st, en, part) in segs]
+        text = [t for d in cur for t in d["tokens"] if t < tk.eot]
+        s.window_alignments.append(alignment)
+        s.last_speech_timestamp = add_word_timestamps(
+            tk, cur, find_alignment(tk, text, alignment), s.seek, s.last_speech_timestamp,
+            prepend_punctuations, append_punctuations)
+        nseek = word_seek(cur, s.seek, nseek, single)
+        segs = [(d["start"], d["end"], d["tokens"]) for d in cur]
+        words = [[Word(w["start"], w["end"], w["word"], w["probability"]) for w in d["words"]] for d in cur]
+    for (st, en, part), ws in zip(segs, words):
         txt = tk.decode(part)
         if st == en or not txt.strip():
             continue
         s.all_tokens.extend(part)
         s.segments.append(Segment(len(s.segments), s.seek, st, en, txt, part,
                                   r.temperature, r.avg_logprob, r.compression_ratio,
-                                  r.no_speech_prob, c0.needs_fallback))
+                                  r.no_speech_prob, c0.needs_fallback, ws))
+    s.window_seeks.append((s.seek, size, nseek))
     s.seek = nseek
     # condition_on_previous_text: a result settled above prompt_reset_on_temperature
     # restarts the prompt after these segments
@@ -411,7 +582,9 @@ def gather_windows(items, n_frames: int = N_FRAMES, device=None):
 
 def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_length: int = 448,
                       temperatures=TEMPERATURES, best_of: int = BEST_OF, utt_keys=None,
-                      speculative: bool = False, beam_size: int = 1, length_penalty: float = 1.0):
+                      speculative: bool = False, beam_size: int = 1, length_penalty: float = 1.0,
+                      word_timestamps: bool = False, prepend_punctuations: str = PREPEND_PUNCTUATIONS,
+                      append_punctuations: str = APPEND_PUNCTUATIONS):
     """faster-whisper's seek loop for several 16 kHz utterances at once: every round
     decodes the current window of each unfinished utterance as one GPU batch (per-row
     prompts), then the temperature fallback of the windows whose gates failed
@@ -428,6 +601,11 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     within one decode call's rows), as in faster-whisper; the fallback temperatures stay the
     sampled best_of decodes and the gates read the winner's sum_logprob / (n + 1). The
     speculative one-call form is greedy only.
+    ``word_timestamps``: every settled window of a round that is not skipped as silence is
+    aligned in ONE engine.align call (the windows share the round's encoder output through
+    enc_index), its segments carry ``words`` and its seek follows rule 8 (include/janus.h,
+    DESIGN.md §5l); ``prepend_punctuations`` / ``append_punctuations`` as in faster-whisper.
+    Off (the default), no call and no result differs.
     Returns one _Stream (segments + gate counters) per utterance."""
     check_beam_args(beam_size, length_penalty)
     if beam_size > 1 and speculative:
@@ -496,8 +674,16 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
                 n_tok = out.n_tokens.cpu().numpy()
             first, final, ndec = settle_round(engine, tk, t0, prompts, keys, enc, max_length,
                                               temperatures, best_of, presampled=pres)
-            for s, size, c0r, r, nd, nt in zip(grp, sizes, first, final, ndec, n_tok):
-                advance(tk, s, size, c0r, r, nd, nt)
+            if not word_timestamps:
+                for s, size, c0r, r, nd, nt in zip(grp, sizes, first, final, ndec, n_tok):
+                    advance(tk, s, size, c0r, r, nd, nt)
+                continue
+            texts = [[] if (r.no_speech_prob > NO_SPEECH_THRESHOLD and not r.avg_logprob > LOG_PROB_THRESHOLD)
+                     else window_text_tokens(tk, r.tokens, s.seek, size)
+                     for s, size, r in zip(grp, sizes, final)]
+            al = engine.align(enc, texts, sizes, enc_index=list(range(len(grp))))
+            for s, size, c0r, r, nd, nt, a in zip(grp, sizes, first, final, ndec, n_tok, al):
+                advance(tk, s, size, c0r, r, nd, nt, True, a, prepend_punctuations, append_punctuations)
     return streams
 
 
@@ -535,11 +721,19 @@ class WhisperModel:
 
     def transcribe(self, audio, beam_size: int = 1, language: str = "en",
                    temperature=TEMPERATURES, best_of: int = BEST_OF, length_penalty: float = 1.0,
-                   patience: float = 1, max_length: int = 448, **_ignored):
+                   patience: float = 1, max_length: int = 448, word_timestamps: bool = False,
+                   prepend_punctuations: str = PREPEND_PUNCTUATIONS,
+                   append_punctuations: str = APPEND_PUNCTUATIONS,
+                   hallucination_silence_threshold=None, **_ignored):
         """faster-whisper's transcribe: ``beam_size`` 1 (greedy, the reference's call) .. 8
         (beam search at T = 0, DESIGN.md §5k), ``length_penalty`` > 0, ``patience`` 1;
-        ``max_length``: the decoder's token limit per window (448)."""
+        ``max_length``: the decoder's token limit per window (448). ``word_timestamps``: every
+        segment carries ``words`` ([Word(start, end, word, probability)]) from the alignment
+        pass, with faster-whisper's ``prepend_punctuations`` /
+        ``append_punctuations``; ``hallucination_silence_threshold`` is not built (None only)."""
         check_beam_args(beam_size, length_penalty, patience)
+        if hallucination_silence_threshold is not None:
+            raise NotImplementedError("hallucination_silence_threshold is not supported")
         if language not in (None, "en"):
             raise NotImplementedError("*.en models transcribe English only (transcriber.py:56)")
         if isinstance(audio, str):
@@ -547,7 +741,10 @@ class WhisperModel:
         audio = np.ascontiguousarray(audio, dtype=np.float32)
         temps = (float(temperature),) if np.isscalar(temperature) else tuple(temperature)
         st = generate_segments(self.engine, [audio], max_length=max_length, temperatures=temps,
-                               best_of=best_of, beam_size=beam_size, length_penalty=length_penalty)[0]
+                               best_of=best_of, beam_size=beam_size, length_penalty=length_penalty,
+                               word_timestamps=bool(word_timestamps),
+                               prepend_punctuations=prepend_punctuations,
+                               append_punctuations=append_punctuations)[0]
         self._count(st)
         info = TranscriptionInfo("en", 1.0, len(audio) / 16000.0)
         return iter(st.segments), info
@@ -603,7 +800,8 @@ class Transcriber:
         return [' '.join(s.text.strip() for s in st.segments).strip() for st in streams]
 
 
-__all__ = ["Transcriber", "WhisperModel", "Segment", "TranscriptionInfo", "read_wav_16k",
+__all__ = ["Transcriber", "WhisperModel", "Segment", "Word", "find_alignment", "merge_punctuations",
+           "add_word_timestamps", "word_seek", "window_text_tokens", "TranscriptionInfo", "read_wav_16k",
            "generate_segments", "settle_round", "advance", "gather_windows", "split_window", "compression_ratio", "gates", "nat",
            "Candidate", "candidate", "best_hypothesis", "settle", "fallback_seed", "TEMPERATURES",
            "BEST_OF"]

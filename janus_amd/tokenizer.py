@@ -120,6 +120,41 @@ class WhisperTokenizer:
         s.update([TRANSCRIBE, TRANSLATE, SOT, SOT_PREV, SOT_LM])
         return sorted(s)
 
+    def split_to_word_tokens(self, tokens):
+        """faster-whisper's Tokenizer.split_to_word_tokens for English (split_tokens_on_spaces
+        over split_tokens_on_unicode): (words, word_tokens). First the tokens are cut where
+        the incremental decode of the tokens gathered so far holds no U+FFFD (a multi-byte
+        character split over tokens stays in one piece) — or holds one that the decode of the
+        whole sequence has at the same place, i.e. the text itself carries it (bytes that
+        are no UTF-8 at all); then a piece starts a new word when its first token is >= eot,
+        or it starts with a space, or its stripped text is in string.punctuation, or it is
+        the first piece — otherwise it is appended to the previous word. Works on the table
+        vocabulary and on a tokenizer.json alike (both decode ids >= eot to nothing)."""
+        import string
+        full = self.decode(tokens)
+        pieces, piece_tokens, cur, offset = [], [], [], 0
+        for t in tokens:
+            cur.append(int(t))
+            text = self.decode(cur)
+            at = text.find("\ufffd")
+            if at < 0 or (offset + at < len(full) and full[offset + at] == "\ufffd"):
+                pieces.append(text)
+                piece_tokens.append(cur)
+                cur = []
+                offset += len(text)
+        words, word_tokens = [], []
+        for text, toks in zip(pieces, piece_tokens):
+            special = toks[0] >= self.eot
+            with_space = text.startswith(" ")
+            punctuation = text.strip() in string.punctuation
+            if special or with_space or punctuation or not words:
+                words.append(text)
+                word_tokens.append(list(toks))
+            else:
+                words[-1] = words[-1] + text
+                word_tokens[-1].extend(toks)
+        return words, word_tokens
+
     def segments(self, sampled):
         """Split sampled tokens (up to, excluding, <|endoftext|>) the way faster-whisper's
         single-window greedy path does; returns list of (start_ts, end_ts, text)."""

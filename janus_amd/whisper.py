@@ -291,6 +291,45 @@ def encoder_compute_mode(name) -> int:
     return ENCODER_COMPUTE[name]
 
 
+ALIGN_MAX_HEADS = 64   # alignment heads of one engine (csrc/align_plan.h kAlignMaxHeads)
+
+
+def default_alignment_heads(cfg):
+    """Every head of the last half of the decoder layers (CTranslate2's default for a
+    checkpoint that names no alignment heads)."""
+    return [(l, h) for l in range(cfg.dec_layers // 2, cfg.dec_layers) for h in range(cfg.n_heads)]
+
+
+def check_alignment_heads(cfg, heads):
+    """[(layer, head)] validated against the model: non-empty, at most ALIGN_MAX_HEADS,
+    indices in range, no pair twice. ValueError otherwise."""
+    try:
+        out = [(int(l), int(h)) for (l, h) in heads]
+    except (TypeError, ValueError):
+        raise ValueError(f"alignment_heads must be (layer, head) pairs, not {heads!r}") from None
+    if not out:
+        raise ValueError("alignment_heads must not be empty")
+    if len(out) > ALIGN_MAX_HEADS:
+        raise ValueError(f"alignment_heads: {len(out)} heads, the limit is {ALIGN_MAX_HEADS}")
+    for l, h in out:
+        if not (0 <= l < cfg.dec_layers and 0 <= h < cfg.n_heads):
+            raise ValueError(f"alignment head ({l}, {h}) out of range for {cfg.name} "
+                             f"({cfg.dec_layers} decoder layers, {cfg.n_heads} heads)")
+    if len(set(out)) != len(out):
+        raise ValueError("alignment_heads: a pair is listed twice")
+    return out
+
+
+@dataclasses.dataclass
+class Alignment:
+    """One window's alignment (janus_whisper_align): the DTW path over (row of text + [eot],
+    encoder frame) and the forced-token probabilities of the text tokens."""
+    text_indices: np.ndarray   # int32 [L]
+    time_indices: np.ndarray   # int32 [L]
+    token_probs: np.ndarray    # float32 [len(text)]
+    attention: np.ndarray = None   # float32 [len(text) + 1][size // 2] (return_attention)
+
+
 class WhisperEngine:
     """One janus_whisper context on the current GPU (thread-safe per call in C++).
 
@@ -300,8 +339,10 @@ class WhisperEngine:
     both."""
 
     def __init__(self, cfg: WhisperConfig, weights: dict = None, seed: int = 0,
-                 encoder_compute: str = "float16"):
+                 encoder_compute: str = "float16", alignment_heads=None):
         mode = encoder_compute_mode(encoder_compute)
+        if alignment_heads is not None:
+            alignment_heads = check_alignment_heads(cfg, alignment_heads)
         self.device = nat.require_gpu()
         self.cfg = cfg
         self.tokenizer = tok.load_tokenizer()
@@ -320,6 +361,10 @@ class WhisperEngine:
             nat.call("janus_whisper_set_tensor", self._h, name.encode(), a.ctypes.data, a.size)
         if mode != ENCODER_COMPUTE["float16"]:
             nat.call("janus_whisper_set_encoder_compute", self._h, mode)
+        self.alignment_heads = alignment_heads or default_alignment_heads(cfg)
+        if alignment_heads is not None:
+            pairs = np.ascontiguousarray(np.asarray(alignment_heads, np.int32).reshape(-1, 2))
+            nat.call("janus_whisper_set_alignment_heads", self._h, pairs.ctypes.data, len(pairs))
 
     @property
     def encoder_compute(self) -> str:
@@ -561,6 +606,62 @@ class WhisperEngine:
                  tokens.data_ptr(), ntok.data_ptr(), slp.data_ptr(), nsp.data_ptr(), nat.stream_ptr())
         del keep, pr
         return DecodeOut(tokens, ntok, slp, nsp, plens)
+
+    def align(self, enc: torch.Tensor, texts, sizes, enc_index=None, return_attention: bool = False,
+              phases: int = 0):
+        """janus_whisper_align: word alignment of several windows in one call. ``texts``: one
+        list of text token ids (< eot, the window's segments concatenated) per window;
+        ``sizes``: each window's content size in mel frames (2 .. 3000); ``enc_index``: window
+        j attends to enc[enc_index[j]] (default enc[j]). Returns one Alignment per window (None
+        for a window without text, which runs nothing): the DTW path over the rows of
+        text + [eot] and the frames < size // 2, and the text tokens' forced probabilities
+        (include/janus.h rules 1 - 5). ``return_attention`` also returns the
+        matrix A the path was solved on; ``phases``: janus_whisper_align's measurement mask."""
+        t = self.tokenizer
+        if len(texts) != len(sizes) or (enc_index is not None and len(enc_index) != len(texts)):
+            raise ValueError("align: one text, one size (and one enc_index) per window")
+        sot = list(t.sot_sequence)
+        live = [j for j, x in enumerate(texts) if len(x) > 0]
+        out = [None] * len(texts)
+        if not live:
+            return out
+        seqs = [sot + [t.no_timestamps] + [int(v) for v in texts[j]] + [t.eot] for j in live]
+        lens = np.array([len(q) for q in seqs], np.int32)
+        if lens.max() > self.cfg.n_text_ctx:
+            raise ValueError(f"align: a sequence of {int(lens.max())} tokens exceeds n_text_ctx "
+                             f"{self.cfg.n_text_ctx}")
+        szs = np.array([int(sizes[j]) for j in live], np.int32)
+        if szs.min() < 2 or szs.max() > 2 * self.cfg.n_audio_ctx:
+            raise ValueError("align: sizes must lie in [2, 3000] mel frames")
+        stride = int(lens.max())
+        toks = np.zeros((len(live), stride), np.int32)
+        for k, q in enumerate(seqs):
+            toks[k, :len(q)] = q
+        ei = np.array([int(enc_index[j]) if enc_index is not None else j for j in live], np.int32)
+        if ei.min() < 0 or ei.max() >= enc.shape[0]:
+            raise ValueError("align: enc_index out of range")
+        assert enc.dtype == torch.float16 and enc.is_contiguous()
+        N = lens - len(sot) - 2 + 1
+        F = szs // 2
+        ps = int((N + F).max())
+        ti = torch.empty(len(live), ps, dtype=torch.int32, device=self.device)
+        fi = torch.empty(len(live), ps, dtype=torch.int32, device=self.device)
+        pl = torch.empty(len(live), dtype=torch.int32, device=self.device)
+        pr = torch.empty(len(live), stride, dtype=torch.float32, device=self.device)
+        aoff = np.concatenate([[0], np.cumsum(N.astype(np.int64) * F)])
+        att = torch.empty(int(aoff[-1]), dtype=torch.float32, device=self.device) if return_attention else None
+        nat.call("janus_whisper_align", self._h, enc.data_ptr(), int(enc.shape[0]), len(live),
+                 toks.ctypes.data, lens.ctypes.data, stride, szs.ctypes.data, ei.ctypes.data, len(sot),
+                 int(t.eot), ti.data_ptr(), fi.data_ptr(), pl.data_ptr(), ps, pr.data_ptr(),
+                 att.data_ptr() if att is not None else None, int(phases), nat.stream_ptr())
+        ti, fi, pl, pr = ti.cpu().numpy(), fi.cpu().numpy(), pl.cpu().numpy(), pr.cpu().numpy()
+        att = att.cpu().numpy() if att is not None else None
+        for k, j in enumerate(live):
+            L = int(pl[k])
+            out[j] = Alignment(ti[k, :L].copy(), fi[k, :L].copy(), pr[k, :int(N[k]) - 1].copy(),
+                               att[aoff[k]:aoff[k + 1]].reshape(int(N[k]), int(F[k])).copy()
+                               if att is not None else None)
+        return out
 
     def decode_stand(self, batch: int, state_slot: int = 0):
         """Where each of the last decode call's ``batch`` row slots stands in decoder state
