@@ -367,6 +367,17 @@ typedef struct {
    * enc_index; steps >= 0; pos_offset + steps <= max_length. NULL = every row fresh. */
   const int32_t* pos_offset;
   int steps;
+  /* Where no_speech_prob is read: row b's no_speech_prob is the raw softmax probability of
+   * no_speech_token from the logits at position prompt_lens[b] - 1 - no_speech_back. 0 (the
+   * *.en models, whose prompt ends in <|startoftranscript|>): the prompt's last position,
+   * i.e. the first sampled step. The multilingual models' prompt ends in [sot, language,
+   * task], so <|startoftranscript|> lies two positions earlier: no_speech_back 2. The
+   * vocabulary projection then runs from the earliest such position on; the rows keep their
+   * forced tokens there and no rule state, counter or token is touched. Applies to every
+   * decode form (greedy, sampled, per-row temperatures, shared encoder rows, staggered
+   * fresh rows, persistent, beam). Each row needs 0 <= no_speech_back < prompt_lens[b], else
+   * the call is rejected (non-zero status, janus_last_error). */
+  int no_speech_back;
 } janus_decode_rows;
 
 /*
@@ -563,6 +574,33 @@ int janus_whisper_align(janus_whisper* w, const uint16_t* enc, int n_enc, int n_
                         int32_t* text_indices, int32_t* time_indices, int32_t* path_lens,
                         int path_stride, float* token_probs, float* attn_out, int phases,
                         void* stream);
+
+/*
+ * Language identification for the multilingual models (faster-whisper's language=None /
+ * WhisperModel.detect_language -> CTranslate2 Whisper.detect_language). CTranslate2's
+ * detect_language cannot be pinned offline (parity unpinned, as the beam and alignment rules
+ * above); the rule built here, as CTranslate2's is publicly described, per window:
+ *  1. One decoder position holding <|startoftranscript|> (sot_token) at position 0 runs over
+ *     the window's encoder output enc [1500][d] (self-attention over itself, cross-attention
+ *     over all 1500 frames; fp16 weights, fp32 accumulation — the decode call's kernels).
+ *  2. The final LayerNorm of its fp32 residual row, in fp32.
+ *  3. Logits for the n_lang language tokens only: the row against embedding rows lang_begin ..
+ *     lang_begin + n_lang - 1 (fp16 weights, fp32 products and sums).
+ *  4. probs = the fp32 softmax over those n_lang logits (no other token takes part).
+ *  5. best = the argmax, the lowest index on ties.
+ * enc [device] fp16 [batch][1500][d]; probs [device] f32 [batch][n_lang]; best [device] int32
+ * [batch] (an index into the language tokens, not a token id). Any batch >= 1: the call runs
+ * chunks of 64 windows. It runs through the decode call's plan and kernels on a lane of its
+ * own — no decoder state slot (KV cache, tokens, graphs, stand) is disturbed, so it may run
+ * between two staggered decode calls — and replaces the vocabulary projection by a head that
+ * reads n_lang x d x 2 bytes of the embedding. 1 <= n_lang <= 128, lang_begin + n_lang <=
+ * n_vocab, else non-zero status (janus_last_error). The context does not know its tokenizer:
+ * a *.en model answers too, meaninglessly; callers gate on the model (janus_amd.whisper
+ * WhisperEngine.detect_language raises there).
+ */
+int janus_whisper_detect_language(janus_whisper* w, const uint16_t* enc, int batch, int sot_token,
+                                  int lang_begin, int n_lang, float* probs, int32_t* best,
+                                  void* stream);
 
 /* ------------------------------------------------------------ vocoder --- */
 /*

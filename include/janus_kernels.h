@@ -282,6 +282,17 @@ int janus_align_token_prob_f16(const float* x, const float* gamma, const float* 
                                const uint16_t* W, int rows, int d, int V, const int32_t* target,
                                float* prob, void* stream);
 
+/*
+ * The language head of janus_whisper_detect_language (langid.hip), one block per row:
+ * probs[r] = softmax over l < n_lang of LayerNorm(x[r]; gamma, beta, 1e-5) . emb[lang_begin + l]
+ * in fp32, best[r] = its argmax (lowest index on ties). x f32 [rows][d], emb fp16 with at
+ * least lang_begin + n_lang rows of d, probs f32 [rows][n_lang], best int32 [rows]; device
+ * pointers. 1 <= n_lang <= 128, d % 8 == 0, d <= 2048.
+ */
+int janus_lang_head_f16(const float* x, const float* gamma, const float* beta, const uint16_t* emb,
+                        int d, int lang_begin, int n_lang, int rows, float* probs, int32_t* best,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,9 @@ SIGNATURES = {
     "janus_align_dtw_f32": [_P, _I32, _I32, _P, _P, _P, _P, _P],
     "janus_align_reduce_f32": [_P, _I32, _I32, _I32, _I32, _P, _P],
     "janus_align_token_prob_f16": [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P],
+    # language identification
+    "janus_whisper_detect_language": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P],
+    "janus_lang_head_f16": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P],
     # test-only view of the decode planner (no engine, no device)
     "janus_decode_plan_describe": [_P, _P, _P, _I32, _I32, _I32, _I32, _F32, _P, _I32, _P, _I32, _I32,
                                    _P, _I32, _P, _I32, _P],

@@ -109,6 +109,12 @@ __global__ __launch_bounds__(256) void beam_step_kernel(
   const int k = st.k, n2k = 2 * k, b0 = wdw * k;
   const int pl = plen[b0];  // the window's rows share its prompt
   if (pos + 1 < pl) {       // inside the prompt: the forced tokens stay, parents the identity
+    // no_speech_prob read before the prompt's end (janus_decode_rows.no_speech_back), as
+    // select_row: beam 0's raw statistics, nothing else touched (block-uniform)
+    if (nsp && pos + 1 + R.target_back == pl) {
+      const LogitPart q = row_parts_reduce(parts + (int64_t)b0 * nblk, nblk, sh);
+      if (tid == 0) nsp[b0] = R.target >= 0 ? __expf(q.t_v - (q.m_raw + __logf(q.s_raw))) : 0.f;
+    }
     if (tid == 0) st.moved[wdw] = 0;
     return;
   }
@@ -133,7 +139,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(
     __syncthreads();  // sh free again
     const LogitPart q = row_parts_reduce(parts + (int64_t)(b0 + j) * nblk, nblk, sh);
     if (tid == 0) {
-      if (j == 0 && nsp && pos + 1 == pl)
+      if (j == 0 && nsp && pos + 1 + R.target_back == pl)
         nsp[b0] = R.target >= 0 ? __expf(q.t_v - (q.m_raw + __logf(q.s_raw))) : 0.f;
       const float lse_all = q.m_all + __logf(q.s_all);
       float lse = lse_all;

@@ -536,7 +536,9 @@ struct DecodeStep : LaneBuffers {
                              nsp, roff);
   }
 
-  void operator()(int pos) const {
+  // the embedding and every layer of position pos: the residual rows x before the final
+  // LayerNorm (the decode call's tail, or the language head of detect_lane, comes after)
+  void forward(int pos) const {
     if (!(P.fuse_se && pos >= P.sample_begin && pos > 0))
       embed_launch(w->tok16.as<_Float16>(), pos_emb, tokens, maxlen, pos, d, x,
                    fused_ln ? lnp : nullptr, B, s, w->dec[0].ln1g, w->dec[0].ln1b,
@@ -554,6 +556,10 @@ struct DecodeStep : LaneBuffers {
       else projected_cross_attention(l, pos);
       mlp(l, pos);
     }
+  }
+
+  void operator()(int pos) const {
+    forward(pos);
     if (pos + 1 < P.sample_begin) return;  // still inside the prompt
     tail(pos);
   }
@@ -679,9 +685,64 @@ static void decode_lane(janus_whisper* w, DecLane& Z, const DecodeCall& call, in
   finish(Z, P, b, call, bst, s);
 }
 
+// Language identification of up to kLangRows windows (janus_whisper_detect_language): the
+// decode call's own machinery — a plan with the one-token prompt [sot] and one position (so
+// the prepared weights, the cross-attention path and the launch geometry are the decode
+// call's), run on the context's language lane — with the tail replaced by the language head
+// (langid.hip) over the position's residual rows. Launched directly: one position, once.
+constexpr int kLangRows = 64;
+static void detect_lane(janus_whisper* w, DecLane& Z, const _Float16* enc, int B, int sot, int lang_begin,
+                        int n_lang, float* probs, int32_t* best, hipStream_t s) {
+  janus_decode_options opt{};
+  const int32_t prompt[1] = {sot};
+  opt.prompt = prompt; opt.prompt_len = 1; opt.max_length = 2;
+  opt.eot = -1; opt.blank_token = -1; opt.timestamp_begin = -1; opt.no_timestamps = -1;
+  opt.max_initial_timestamp_index = -1;
+  opt.check_every = 0;
+  opt.path_flags = JANUS_DEC_PATH_NO_GRAPH;
+  const DecodePlan P = plan_decode(w->cfg, opt, nullptr, nullptr, nullptr, B, stream_cu_count(s), false,
+                                   LaneStand{&Z.stand, Z.stand_maxlen}, SegDevice{dec_seg_grid, dec_seg_resident});
+  Z.stand.clear();
+  const LaneBuffers b = ensure_buffers(w, Z, P, 0, s);
+  const BeamState bst{};
+  const DecodeCall call{enc, &opt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  upload_inputs(w, Z, P, b, call, bst, s);
+  project_cross_kv(w, P, b, s);
+  const DecodeStep step(w, P, b, bst, s);
+  step.forward(0);
+  lang_head_launch(b.x, step.fin_g, step.fin_b, w->tok16.as<_Float16>(), w->cfg.d_model, w->cfg.n_vocab,
+                   lang_begin, n_lang, B, probs, best, s);
+}
+
 }  // namespace janus
 
 using namespace janus;
+
+extern "C" int janus_whisper_detect_language(janus_whisper* w, const uint16_t* enc, int batch, int sot_token,
+                                             int lang_begin, int n_lang, float* probs, int32_t* best,
+                                             void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(w && enc && probs && best, "null argument");
+    JANUS_CHECK(batch >= 1, "detect_language: batch must be >= 1");
+    const int V = w->cfg.n_vocab;
+    JANUS_CHECK(sot_token >= 0 && sot_token < V, "detect_language: sot_token out of range");
+    JANUS_CHECK(n_lang >= 1 && n_lang <= 128 && lang_begin >= 0 && lang_begin + n_lang <= V,
+                "detect_language: need 1 <= n_lang <= 128 and lang_begin + n_lang <= n_vocab");
+    JANUS_CHECK(w->cfg.d_model % 8 == 0, "detect_language: d_model % 8 != 0");
+    std::lock_guard<std::mutex> lk(w->mu);
+    hipStream_t s = (hipStream_t)stream;
+    prepare(w, s);
+    if (!w->lang_lane) w->lang_lane.reset(new DecLane());
+    const _Float16* e = reinterpret_cast<const _Float16*>(enc);
+    const int64_t erow = (int64_t)w->cfg.n_audio_ctx * w->cfg.d_model;
+    // larger batches in chunks of kLangRows windows, as the decode entry's lanes slice a batch
+    for (int b0 = 0; b0 < batch; b0 += kLangRows) {
+      const int n = std::min(kLangRows, batch - b0);
+      detect_lane(w, *w->lang_lane, e + b0 * erow, n, sot_token, lang_begin, n_lang,
+                  probs + (int64_t)b0 * n_lang, best + b0, s);
+    }
+  });
+}
 
 extern "C" int janus_whisper_decode_greedy(janus_whisper* w, const uint16_t* enc, int batch,
                                            const janus_decode_options* opt, int32_t* tokens,
@@ -772,6 +833,7 @@ extern "C" int janus_whisper_decode_beam_ex(janus_whisper* w, const uint16_t* en
     janus_decode_rows br{};
     br.prompts = prompts.data(); br.prompt_lens = plens.data(); br.stride = stride;
     br.no_speech_token = rows ? rows->no_speech_token : -1;
+    br.no_speech_back = rows ? rows->no_speech_back : 0;
     br.enc_index = eidx.data(); br.n_enc = n_windows;
     const BeamMode bm{k, length_penalty};
     // (shared encoder rows: one lane; a null stream gets the lane's own, as every decode)

@@ -160,9 +160,15 @@ static void plan_rows(DecodePlan& P, const janus_whisper_config& c, const janus_
   const int max_plen = f1 > f0 ? *std::max_element(h_plen.begin() + f0, h_plen.begin() + f1) : 1;
   JANUS_CHECK(min_plen >= 1 && max_plen < maxlen && maxlen <= NC,
               "decode: need 1 <= prompt_len < max_length <= n_text_ctx");
-  // index of the first sampled token (earliest row); staggered continuing rows sample from
-  // the first step on
-  P.sample_begin = (stagger && f1 - f0 < B) ? 0 : min_plen;
+  // no_speech_prob read no_speech_back positions before each row's last prompt position (the
+  // <|startoftranscript|> position of a [sot, language, task] prompt): inside every prompt
+  const int back = P.nsp_back = rows ? rows->no_speech_back : 0;
+  for (int b = 0; b < B; ++b)
+    JANUS_CHECK(back >= 0 && back < h_plen[b], "decode: need 0 <= no_speech_back < prompt_len in every row");
+  // index of the first position whose logits are read — the first sampled token, or the
+  // earliest no-speech position before it (earliest row): the vocabulary projection runs from
+  // there on; staggered continuing rows sample from the first step on
+  P.sample_begin = (stagger && f1 - f0 < B) ? 0 : min_plen - (f1 > f0 ? back : 0);
 }
 
 // Sampling: the rules' temperature and the per-row 1 / T.
@@ -186,6 +192,7 @@ static void plan_sampling(DecodePlan& P, const janus_decode_options& opt, const 
   R.no_timestamps = opt.no_timestamps;
   R.max_initial_ts = opt.max_initial_timestamp_index;
   R.target = rows ? rows->no_speech_token : -1;
+  R.target_back = P.nsp_back;
   // per-row temperatures: R.inv_temp only selects the sampling kernel (rows read their own)
   R.inv_temp = !sampling ? 0.f : smp->temps ? 1.0f : 1.0f / smp->temperature;
 }

@@ -68,6 +68,7 @@ struct DecodePlan {
   int sample_begin = 0;     // index of the first sampled token (earliest row)
   int f0 = 0, f1 = 0;       // the fresh rows [f0, f1) (not staggered: every row)
   int max_roff = 0;
+  int nsp_back = 0;         // janus_decode_rows.no_speech_back
   int nwin = 0, beam_k = 0; // beam search: windows and beams per window (0: off)
   // ---- paths
   int enc_rows = JANUS_ENC_ROWS_OWN;   // how the rows reach their encoder output
@@ -118,7 +119,7 @@ struct DecodePlan {
     step("R.eot", R.eot); step("R.suppress_blank", R.suppress_blank); step("R.blank", R.blank);
     step("R.ts_begin", R.ts_begin); step("R.no_timestamps", R.no_timestamps);
     step("R.max_initial_ts", R.max_initial_ts); step("R.target", R.target);
-    step("R.inv_temp", R.inv_temp);
+    step("R.inv_temp", R.inv_temp); step("no_speech_back", nsp_back);
     call("steps", steps); call("check_every", check_every); call("f0", f0); call("f1", f1);
     call("enc_rows", enc_rows); call("n_enc", n_enc); call("use_graph", use_graph); call("cus", cus);
   }

@@ -22,6 +22,8 @@ struct DecodeRules {
   float inv_temp;                // 0: greedy (argmax); > 0: sample at temperature 1 / inv_temp
                                  // (Gumbel-max over the rule-filtered logits, noise from
                                  // sample_noise(seed of the row, position, token))
+  int target_back = 0;           // target's probability is read target_back positions before the
+                                 // row's last prompt position (janus_decode_rows.no_speech_back)
 };
 
 bool resid_ln_supported(int N, int K);

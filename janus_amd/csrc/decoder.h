@@ -96,9 +96,10 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
 // these are (the sampled token goes to pos + 1); row_inv_temp [B] (device, nullable): row
 // b samples at 1 / row_inv_temp[b] instead of R.inv_temp (several temperatures in one call)
 // plen [B] (device, nullable = all rows sample from pos + 1 >= 1): rows with pos + 1 <
-// plen[b] are still inside their own prompt and keep the forced token. At a row's first
-// sampled step (pos + 1 == plen[b]) nsp[b] (nullable) gets the raw softmax probability of
-// DecodeRules::target (Whisper's no_speech_prob).
+// plen[b] are still inside their own prompt and keep the forced token. At the step with
+// pos + 1 + R.target_back == plen[b] (target_back 0: the row's first sampled step; > 0: a
+// prompt position, where nothing else is touched) nsp[b] (nullable) gets the raw softmax
+// probability of DecodeRules::target (Whisper's no_speech_prob).
 void select_partials_launch(const LogitPart* parts, int nblk, const DecodeRules& R,
                             RowRules* rules, int32_t* tokens, int ld, int pos, int32_t* done,
                             float* sum_lp, int32_t* n_tok, int B, hipStream_t s,

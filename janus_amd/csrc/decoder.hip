@@ -789,7 +789,16 @@ __device__ __forceinline__ int select_row(
   }
   int32_t* row_tok = tokens + (int64_t)b * ld;
   const int pl = plen ? plen[b] : 1;
-  if (pos + 1 < pl) return row_tok[pos + 1];  // inside this row's prompt: the forced token stays
+  if (pos + 1 < pl) {  // inside this row's prompt: the forced token stays
+    // no_speech_prob read before the prompt's end (the <|startoftranscript|> position of a
+    // [sot, language, task] prompt): the raw statistics alone, no rule state, counter or
+    // token touched (block-uniform: pos, pl and R are)
+    if (nsp && pos + 1 + R.target_back == pl) {
+      const LogitPart q = row_parts_reduce(parts + (int64_t)b * nblk, nblk, sh);
+      if (tid == 0) nsp[b] = R.target >= 0 ? __expf(q.t_v - (q.m_raw + __logf(q.s_raw))) : 0.f;
+    }
+    return row_tok[pos + 1];
+  }
   if (done[b]) {
     if (tid == 0) row_tok[pos + 1] = R.eot;
     return R.eot;
@@ -802,7 +811,7 @@ __device__ __forceinline__ int select_row(
   const int ba_i = q.b_all_i, bt_i = q.b_ts_i;
   // no_speech_prob: the raw softmax probability of the target token at the row's first
   // sampled step (logits at the <|startoftranscript|> position, before any filter)
-  if (nsp && pos + 1 == pl) nsp[b] = R.target >= 0 ? __expf(t_v - (m_raw + __logf(s_raw))) : 0.f;
+  if (nsp && pos + 1 + R.target_back == pl) nsp[b] = R.target >= 0 ? __expf(t_v - (m_raw + __logf(s_raw))) : 0.f;
   const float lse_all = m_all + __logf(s_all);
   // the chosen token's log-probability uses its logit (b_*_r; = the key when greedy)
   int next = ba_i;

@@ -412,3 +412,16 @@ extern "C" int janus_align_token_prob_f16(const float* x, const float* gamma, co
     JANUS_HIP(hipStreamSynchronize(s));
   });
 }
+
+// ------------------------------------------------------------------ language head
+extern "C" int janus_lang_head_f16(const float* x, const float* gamma, const float* beta, const uint16_t* emb,
+                                   int d, int lang_begin, int n_lang, int rows, float* probs, int32_t* best,
+                                   void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(x && gamma && beta && emb && probs && best, "null argument");
+    JANUS_CHECK(lang_begin >= 0 && n_lang >= 1, "lang_head: lang_begin >= 0, n_lang >= 1");
+    // (emb's row count is the caller's: it holds at least lang_begin + n_lang rows)
+    lang_head_launch(x, gamma, beta, reinterpret_cast<const _Float16*>(emb), d, lang_begin + n_lang,
+                     lang_begin, n_lang, rows, probs, best, (hipStream_t)stream);
+  });
+}

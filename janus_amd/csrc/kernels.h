@@ -266,4 +266,13 @@ void mel_normalize_launch(const float* logmel, const uint32_t* maxkey, _Float16*
                           const int64_t* offsets, int decim, int B, int frames, int n_mels,
                           int out_ld, hipStream_t s);
 
+// ------------------------------------------------------------------ language head
+// Language identification (langid.hip): per row the final LayerNorm of x [rows][d] fp32, the
+// logits of embedding rows lang_begin .. lang_begin + n_lang - 1 (emb fp16 [n_vocab][d]), an
+// fp32 softmax over them into probs [rows][n_lang] and the argmax (lowest index on ties) into
+// best [rows]. 1 <= n_lang <= 128, d % 8 == 0, d <= 2048, lang_begin + n_lang <= n_vocab.
+void lang_head_launch(const float* x, const float* g, const float* b, const _Float16* emb, int d,
+                      int n_vocab, int lang_begin, int n_lang, int rows, float* probs, int32_t* best,
+                      hipStream_t s);
+
 }  // namespace janus

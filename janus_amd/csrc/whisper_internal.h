@@ -93,6 +93,9 @@ struct janus_whisper {
   // decoder lanes: each owns the workspaces, captured graphs and stream of one batch slice
   std::vector<std::unique_ptr<janus::DecLane>> lanes;
   int last_slot = 0;  // state slot of the last decode call (decode_info reports it)
+  // language identification's own lane (janus_whisper_detect_language): no state slot's KV
+  // cache, tokens, graphs or stand is touched by it
+  std::unique_ptr<janus::DecLane> lang_lane;
   janus::AlignState align;  // word alignment (align_call.cpp): heads, plan and workspaces
   hipEvent_t ev_in = nullptr;
   ~janus_whisper() {

@@ -311,6 +311,10 @@ class JanusPipeline(PacketRenderer):
         whose windows all fail the gates: DESIGN.md §0).
         whisper_compute: "float16" (default) or "int8", the compute type of the Whisper
         encoder's linear layers (WhisperEngine(encoder_compute=...))."""
+        if model in CONFIGS and CONFIGS[model].multilingual:
+            raise NotImplementedError(
+                f"JanusPipeline serves the English-only models; the multilingual {model!r} runs "
+                "through services.transcriber.WhisperModel (language / task prompts)")
         super().__init__(vocoder_cfg, vocoder_seed, vocoder_weights)
         self.whisper = WhisperEngine(CONFIGS[model], seed=whisper_seed, encoder_compute=whisper_compute)
         self.max_length = max_length

@@ -36,6 +36,12 @@ call (beam_size=1, language='en', every other option at its default):
   (``fallback_seed``), so a run is reproducible and the CPU oracle draws the same noise —
   CTranslate2's own random draws cannot be reproduced offline.
 
+Multilingual models (tiny / base / small): ``language`` is a code, or None to detect it on
+the GPU (``WhisperEngine.detect_language`` over the first window's encoder output, which the
+first round computes anyway; ``language_detection_segments`` / ``_threshold`` as in
+faster-whisper), ``task`` is "transcribe" or "translate"; each utterance's prompt ends in its
+own [sot, <|language|>, <|task|>]. On ``*.en`` models none of this runs.
+
 A window that would not advance the seek (a leading <|0.00|><|0.00|>) advances by the
 window size, so the loop always terminates.
 
@@ -52,7 +58,7 @@ import torch
 
 from .. import _native as nat
 from ..common import wavio
-from ..tokenizer import SOT_PREV
+from ..tokenizer import LANGUAGES, SOT_PREV, TASKS
 from ..whisper import CONFIGS, WhisperEngine, check_beam_args, shared_rows_in_place
 
 WINDOW_16K = 480000
@@ -180,6 +186,9 @@ class TranscriptionInfo:
     language: str
     language_probability: float
     duration: float
+    # [(code, probability)] by descending probability when the language was detected; None
+    # for a given language and for *.en models (as faster-whisper)
+    all_language_probs: list = None
 
 
 read_wav_16k = wavio.read_wav_16k  # 16-bit PCM WAV -> f32 @ 16 kHz
@@ -263,14 +272,18 @@ APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
 SENTENCE_END_MARKS = ".。!！?？"
 
 
-def find_alignment(tk, text_tokens, alignment):
+def find_alignment(tk, text_tokens, alignment, language=None):
     """One window's words from its alignment (faster-whisper find_alignment after the
     CTranslate2 call): [dict(word, tokens, start, end, probability)], times in seconds from
     the window's start. ``alignment``: WhisperEngine.align's result for ``text_tokens`` (its
-    text_indices / time_indices / token_probs); None or no text gives no words."""
+    text_indices / time_indices / token_probs); None or no text gives no words. ``language``
+    (multilingual models): the utterance's code, which decides the word split."""
     if alignment is None or len(text_tokens) == 0:
         return []
-    words, word_tokens = tk.split_to_word_tokens(list(text_tokens) + [tk.eot])
+    if language is None:
+        words, word_tokens = tk.split_to_word_tokens(list(text_tokens) + [tk.eot])
+    else:
+        words, word_tokens = tk.split_to_word_tokens(list(text_tokens) + [tk.eot], language)
     if len(word_tokens) <= 1:
         return []
     boundaries = np.pad(np.cumsum([len(t) for t in word_tokens[:-1]]), (1, 0))
@@ -410,6 +423,16 @@ class _Stream:
         self.last_speech_timestamp = 0.0   # word timestamps: the end of the last segment with words
         self.window_seeks = []         # (seek, size, next seek) of every window, in order
         self.window_alignments = []    # word timestamps: every window's Alignment (None: none run)
+        # multilingual models: the utterance's language (given or detected), its probability,
+        # every language's probability [(code, p)] by descending p (detected only) and its
+        # own start sequence [sot, <|language|>, <|task|>] (None: the tokenizer's)
+        self.language = "en"
+        self.language_probability = 1.0
+        self.all_language_probs = None
+        self.sot_sequence = None
+        self.task = "transcribe"
+        self.language_pending = False  # still to be detected (language=None)
+        self.language_votes = []       # (code, probability) of every window examined so far
 
     def transcript(self):
         """transcribe_buffer's join of the segments (transcriber.py:59-64)."""
@@ -424,8 +447,33 @@ class _Stream:
 
     def prompt(self, tk, max_length=448):
         prev = self.all_tokens[self.prompt_reset_since:]
-        p = ([SOT_PREV] + prev[-(max_length // 2 - 1):]) if prev else []   # 223 at 448
-        return p + list(tk.sot_sequence)
+        p = ([getattr(tk, "sot_prev", SOT_PREV)] + prev[-(max_length // 2 - 1):]) if prev else []   # 223 at 448
+        return p + list(self.sot_sequence if self.sot_sequence is not None else tk.sot_sequence)
+
+    def vote_language(self, tk, probs, segments: int, threshold: float, last: bool):
+        """faster-whisper's language detection over one more window's probabilities (f32
+        [n_languages]): the window's winner settles the language at once when its
+        probability exceeds ``threshold``; otherwise the next windows of the seek loop are
+        examined too, up to ``segments`` (or the utterance's ``last`` window), and the
+        majority of the per-window winners is taken, the earliest on ties, with the largest
+        probability that language reached. Until then the windows decode with the majority so
+        far. all_language_probs are those of the last window examined."""
+        probs = np.asarray(probs, np.float64)
+        i = int(np.argmax(probs))
+        self.language_votes.append((LANGUAGES[i], float(probs[i])))
+        order = np.argsort(-probs, kind="stable")
+        self.all_language_probs = [(LANGUAGES[int(k)], float(probs[int(k)])) for k in order]
+        if probs[i] > threshold:
+            self.language, self.language_probability = self.language_votes[-1]
+            self.language_pending = False
+        else:
+            by = {}
+            for code, p in self.language_votes:
+                by.setdefault(code, []).append(p)
+            self.language = max(by, key=lambda code: len(by[code]))   # first inserted on ties
+            self.language_probability = max(by[self.language])
+            self.language_pending = len(self.language_votes) < segments and not last
+        self.sot_sequence = tk.sot_sequence_for(self.language, self.task)
 
 
 def _fallback(engine, tk, enc, prompts, first, keys, max_length, temperatures, best_of,
@@ -525,7 +573,9 @@ def advance(tk, s, size, c0, r, nd, sampled: int = 0, word_timestamps: bool = Fa
         text = [t for d in cur for t in d["tokens"] if t < tk.eot]
         s.window_alignments.append(alignment)
         s.last_speech_timestamp = add_word_timestamps(
-            tk, cur, find_alignment(tk, text, alignment), s.seek, s.last_speech_timestamp,
+            tk, cur, find_alignment(tk, text, alignment,
+                                    s.language if getattr(tk, "multilingual", False) else None),
+            s.seek, s.last_speech_timestamp,
             prepend_punctuations, append_punctuations)
         nseek = word_seek(cur, s.seek, nseek, single)
         segs = [(d["start"], d["end"], d["tokens"]) for d in cur]
@@ -584,7 +634,9 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
                       temperatures=TEMPERATURES, best_of: int = BEST_OF, utt_keys=None,
                       speculative: bool = False, beam_size: int = 1, length_penalty: float = 1.0,
                       word_timestamps: bool = False, prepend_punctuations: str = PREPEND_PUNCTUATIONS,
-                      append_punctuations: str = APPEND_PUNCTUATIONS):
+                      append_punctuations: str = APPEND_PUNCTUATIONS, language=None,
+                      task: str = "transcribe", language_detection_segments: int = 1,
+                      language_detection_threshold: float = 0.5):
     """faster-whisper's seek loop for several 16 kHz utterances at once: every round
     decodes the current window of each unfinished utterance as one GPU batch (per-row
     prompts), then the temperature fallback of the windows whose gates failed
@@ -606,6 +658,12 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     enc_index), its segments carry ``words`` and its seek follows rule 8 (include/janus.h,
     DESIGN.md §5l); ``prepend_punctuations`` / ``append_punctuations`` as in faster-whisper.
     Off (the default), no call and no result differs.
+    ``language`` / ``task`` (multilingual engines only; on a ``*.en`` engine none of it runs):
+    one code for every utterance, a list with one entry per utterance, or None to detect —
+    then each round makes ONE engine.detect_language call over the encoder output it computed
+    anyway, for the utterances still undecided (_Stream.vote_language: faster-whisper's
+    ``language_detection_segments`` / ``language_detection_threshold`` rule); every stream
+    carries its language, probability, all_language_probs and its own start sequence.
     Returns one _Stream (segments + gate counters) per utterance."""
     check_beam_args(beam_size, length_penalty)
     if beam_size > 1 and speculative:
@@ -617,6 +675,22 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     tk = engine.tokenizer
     dev = engine.device
     streams = [_Stream(np.asarray(a, np.float32)) for a in audios]
+    multilingual = bool(getattr(tk, "multilingual", False))
+    if multilingual:
+        if task not in TASKS:
+            raise ValueError(f"unknown task {task!r}: one of {TASKS}")
+        if language_detection_segments < 1:
+            raise ValueError("language_detection_segments must be >= 1")
+        codes = list(language) if isinstance(language, (list, tuple)) else [language] * len(streams)
+        if len(codes) != len(streams):
+            raise ValueError("language: one code (or None) per utterance")
+        for st, code in zip(streams, codes):
+            st.task = task
+            if code is None:
+                st.language_pending = True
+            else:
+                st.language = code
+                st.sot_sequence = tk.sot_sequence_for(code, task)   # ValueError: unknown code
     # the whole clip's features, once per utterance (faster-whisper's FeatureExtractor call)
     feats = []
     for st in streams:
@@ -644,6 +718,13 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
             sizes = [s.window_size() for s in grp]
             mel = gather_windows([(feats[i], 0, s.seek, size) for i, s, size in zip(idx, grp, sizes)])
             enc = engine.encode(mel)
+            pend = [j for j, s in enumerate(grp) if s.language_pending]
+            if pend:
+                lp, _ = engine.detect_language(enc if len(pend) == len(grp) else enc[pend].contiguous())
+                lp = np.asarray(lp.cpu() if hasattr(lp, "cpu") else lp, np.float32)
+                for k, j in enumerate(pend):
+                    grp[j].vote_language(tk, lp[k], language_detection_segments, language_detection_threshold,
+                                         last=grp[j].seek + sizes[j] >= grp[j].content_frames)
             prompts = [s.prompt(tk, max_length) for s in grp]
             keys = [(i if utt_keys is None else int(utt_keys[i]), s.windows) for i, s in zip(idx, grp)]
             pres = None
@@ -681,7 +762,11 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
             texts = [[] if (r.no_speech_prob > NO_SPEECH_THRESHOLD and not r.avg_logprob > LOG_PROB_THRESHOLD)
                      else window_text_tokens(tk, r.tokens, s.seek, size)
                      for s, size, r in zip(grp, sizes, final)]
-            al = engine.align(enc, texts, sizes, enc_index=list(range(len(grp))))
+            if multilingual:   # every window's own start sequence in front of its text
+                al = engine.align(enc, texts, sizes, enc_index=list(range(len(grp))),
+                                  sot_sequences=[s.sot_sequence for s in grp])
+            else:
+                al = engine.align(enc, texts, sizes, enc_index=list(range(len(grp))))
             for s, size, c0r, r, nd, nt, a in zip(grp, sizes, first, final, ndec, n_tok, al):
                 advance(tk, s, size, c0r, r, nd, nt, True, a, prepend_punctuations, append_punctuations)
     return streams
@@ -719,12 +804,64 @@ class WhisperModel:
         self.engine = WhisperEngine(CONFIGS[model_size], encoder_compute=enc_compute)
         self.stats = {"windows": 0, "needs_fallback": 0, "no_speech_skips": 0, "fallback_decodes": 0}
 
-    def transcribe(self, audio, beam_size: int = 1, language: str = "en",
+    @property
+    def is_multilingual(self) -> bool:
+        return bool(getattr(getattr(self.engine, "tokenizer", None), "multilingual", False))
+
+    @property
+    def supported_languages(self):
+        """faster-whisper's supported_languages: the 99 codes, or ["en"] for a ``*.en`` model."""
+        return list(LANGUAGES) if self.is_multilingual else ["en"]
+
+    def _check_language(self, language, task):
+        """``*.en``: English transcription only (NotImplementedError, as before the
+        multilingual models); multilingual: ValueError for an unknown code or task."""
+        if not self.is_multilingual:
+            if language not in (None, "en") or task != "transcribe":
+                raise NotImplementedError("*.en models transcribe English only (transcriber.py:56)")
+            return
+        if task not in TASKS:
+            raise ValueError(f"unknown task {task!r}: one of {TASKS}")
+        if language is not None:
+            self.engine.tokenizer.language_token(language)
+
+    def detect_language(self, audio, language_detection_segments: int = 1,
+                        language_detection_threshold: float = 0.5):
+        """faster-whisper's detect_language: (language, probability, all_language_probs) of
+        16 kHz ``audio`` (or a WAV path) from its first ``language_detection_segments``
+        30 s windows (one encode and one WhisperEngine.detect_language call over them).
+        ValueError on a ``*.en`` model."""
+        if not self.is_multilingual:
+            raise ValueError(f"detect_language: {self.model_size} is English-only")
+        if language_detection_segments < 1:
+            raise ValueError("language_detection_segments must be >= 1")
+        if isinstance(audio, str):
+            audio = read_wav_16k(audio)
+        audio = np.ascontiguousarray(audio, dtype=np.float32)
+        eng, st = self.engine, _Stream(audio)
+        if st.content_frames <= 0:
+            raise ValueError("detect_language: empty audio")
+        pcm = torch.from_numpy(np.concatenate([audio, np.zeros(1, np.float32)])).to(eng.device)
+        offs = torch.tensor([0, len(audio)], dtype=torch.int64, device=eng.device)
+        feats = eng.logmel_frames(pcm, offs, 1, 1, st.content_frames)
+        seeks = list(range(0, st.content_frames, N_FRAMES))[:language_detection_segments]
+        mel = gather_windows([(feats, 0, sk, min(N_FRAMES, st.content_frames - sk)) for sk in seeks])
+        probs, _ = eng.detect_language(eng.encode(mel))
+        probs = probs.cpu().numpy()
+        for k in range(len(seeks)):
+            st.vote_language(eng.tokenizer, probs[k], len(seeks), language_detection_threshold,
+                             last=k + 1 == len(seeks))
+            if not st.language_pending:
+                break
+        return st.language, st.language_probability, st.all_language_probs
+
+    def transcribe(self, audio, beam_size: int = 1, language: str = None, task: str = "transcribe",
                    temperature=TEMPERATURES, best_of: int = BEST_OF, length_penalty: float = 1.0,
                    patience: float = 1, max_length: int = 448, word_timestamps: bool = False,
                    prepend_punctuations: str = PREPEND_PUNCTUATIONS,
                    append_punctuations: str = APPEND_PUNCTUATIONS,
-                   hallucination_silence_threshold=None, **_ignored):
+                   hallucination_silence_threshold=None, language_detection_segments: int = 1,
+                   language_detection_threshold: float = 0.5, **_ignored):
         """faster-whisper's transcribe: ``beam_size`` 1 (greedy, the reference's call) .. 8
         (beam search at T = 0, DESIGN.md §5k), ``length_penalty`` > 0, ``patience`` 1;
         ``max_length``: the decoder's token limit per window (448). ``word_timestamps``: every
@@ -734,8 +871,7 @@ class WhisperModel:
         check_beam_args(beam_size, length_penalty, patience)
         if hallucination_silence_threshold is not None:
             raise NotImplementedError("hallucination_silence_threshold is not supported")
-        if language not in (None, "en"):
-            raise NotImplementedError("*.en models transcribe English only (transcriber.py:56)")
+        self._check_language(language, task)
         if isinstance(audio, str):
             audio = read_wav_16k(audio)
         audio = np.ascontiguousarray(audio, dtype=np.float32)
@@ -744,9 +880,12 @@ class WhisperModel:
                                best_of=best_of, beam_size=beam_size, length_penalty=length_penalty,
                                word_timestamps=bool(word_timestamps),
                                prepend_punctuations=prepend_punctuations,
-                               append_punctuations=append_punctuations)[0]
+                               append_punctuations=append_punctuations, language=language, task=task,
+                               language_detection_segments=language_detection_segments,
+                               language_detection_threshold=language_detection_threshold)[0]
         self._count(st)
-        info = TranscriptionInfo("en", 1.0, len(audio) / 16000.0)
+        info = TranscriptionInfo(st.language, st.language_probability, len(audio) / 16000.0,
+                                 st.all_language_probs)
         return iter(st.segments), info
 
     def _count(self, st):

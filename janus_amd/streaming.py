@@ -118,6 +118,10 @@ class StreamingEncoder:
         transcribe_buffer runs it (the default); (0.0,) decodes each window once at T = 0
         and never re-decodes (the config-5 stream bench's setting on synthetic weights,
         whose windows all fail the gates: DESIGN.md §0)."""
+        if getattr(getattr(whisper, "tokenizer", None), "multilingual", False):
+            raise NotImplementedError(
+                "StreamingEncoder serves the English-only models; a multilingual engine runs "
+                "through services.transcriber.WhisperModel (language / task prompts)")
         self.device = nat.require_gpu()
         self.temperatures = tuple(float(t) for t in temperatures)
         self.S = n_streams

@@ -1,9 +1,15 @@
-"""Whisper English-only token space and detokenisation (host side).
+"""Whisper token spaces (English-only and multilingual) and detokenisation (host side).
 
 Special-token layout of the ``*.en`` Whisper vocabulary (51 864 ids; GPT-2 byte-level
 BPE in 0..50255): <|endoftext|> 50256, <|startoftranscript|> 50257, 99 language tokens,
 <|translate|> 50357, <|transcribe|> 50358, <|startoflm|> 50359, <|startofprev|> 50360,
 <|nocaptions|> 50361, <|notimestamps|> 50362, timestamps <|0.00|>..<|30.00|> from 50363.
+
+The multilingual vocabulary (tiny / base / small; 51 865 ids) has one more BPE token, so
+every special id sits one higher: <|endoftext|> 50257, <|startoftranscript|> 50258, the 99
+language tokens 50259..50357, <|translate|> 50358, <|transcribe|> 50359, <|startoflm|> 50360,
+<|startofprev|> 50361, <|nospeech|> 50362, <|notimestamps|> 50363, timestamps from 50364; its
+start sequence is [sot, <|language|>, <|task|>].
 
 No tokenizer files exist offline. If ``JANUS_WHISPER_DIR`` holds a Hugging Face
 ``tokenizer.json``, it is used through the ``tokenizers`` package; otherwise a
@@ -29,7 +35,18 @@ NO_SPEECH = 50361
 NO_TIMESTAMPS = 50362
 TIMESTAMP_BEGIN = 50363
 N_VOCAB_EN = 51864
+N_VOCAB_MULTILINGUAL = 51865
 BLANK = 220
+
+# the 99 language tokens in openai/whisper's order (tokenizer.LANGUAGES)
+LANGUAGES = ("en zh de es ru ko fr ja pt tr pl ca nl ar sv it id hi fi vi he uk el ms cs ro da hu "
+             "ta no th ur hr bg lt la mi ml cy sk te fa lv bn sr az sl kn et mk br eu is hy ne mn bs "
+             "kk sq sw gl mr pa si km sn yo so af oc ka be tg sd gu am yi lo uz fo ht ps tk nn mt sa "
+             "lb my bo tl mg as tt haw ln ha ba jw su").split()
+TASKS = ("transcribe", "translate")
+# languages written without spaces: words are the unicode pieces (faster-whisper's
+# Tokenizer.split_to_word_tokens)
+UNSPACED_LANGUAGES = frozenset({"zh", "ja", "th", "lo", "my", "yue"})
 
 # openai/whisper tokenizer.non_speech_tokens symbol set
 _SYMBOLS = list("\"#()*+/:;<=>@[\\]^_`{|}~「」『』") + \
@@ -46,36 +63,78 @@ def bytes_to_unicode_order():
 
 
 class WhisperTokenizer:
-    def __init__(self, path: str = None, seed: int = 1234):
-        self.eot, self.sot = EOT, SOT
-        self.timestamp_begin = TIMESTAMP_BEGIN
-        self.no_timestamps = NO_TIMESTAMPS
+    """One token space: ``multilingual=False`` the ``*.en`` ids (the module constants),
+    ``multilingual=True`` the 51 865-entry vocabulary with every special id one higher and
+    the start sequence [sot, <|language|>, <|task|>]."""
+
+    def __init__(self, path: str = None, seed: int = 1234, multilingual: bool = False,
+                 language: str = "en", task: str = "transcribe"):
+        self.multilingual = bool(multilingual)
+        up = 1 if self.multilingual else 0
+        self.eot, self.sot = EOT + up, SOT + up
+        self.translate, self.transcribe = TRANSLATE + up, TRANSCRIBE + up
+        self.sot_lm, self.sot_prev = SOT_LM + up, SOT_PREV + up
+        self.no_speech = NO_SPEECH + up
+        self.no_timestamps = NO_TIMESTAMPS + up
+        self.timestamp_begin = TIMESTAMP_BEGIN + up
+        self.language_begin = self.sot + 1
+        self.n_languages = len(LANGUAGES)
+        self.n_vocab = N_VOCAB_MULTILINGUAL if self.multilingual else N_VOCAB_EN
         self.blank = BLANK
-        self.sot_sequence = [SOT]  # *.en: no language / task tokens
+        self.language, self.task = language, task
+        # *.en: no language / task tokens
+        self.sot_sequence = self.sot_sequence_for(language, task)
         self._hf = None
         if path and os.path.exists(os.path.join(path, "tokenizer.json")):
             from tokenizers import Tokenizer
             self._hf = Tokenizer.from_file(os.path.join(path, "tokenizer.json"))
-            # the decoder's prompt and rules use the *.en special-token ids: the file must agree
-            for name, want in (("<|endoftext|>", EOT), ("<|startoftranscript|>", SOT),
-                               ("<|startofprev|>", SOT_PREV), ("<|notimestamps|>", NO_TIMESTAMPS)):
+            # the decoder's prompt and rules use this layout's special-token ids: the file must agree
+            layout = "multilingual" if self.multilingual else "*.en"
+            for name, want in (("<|endoftext|>", self.eot), ("<|startoftranscript|>", self.sot),
+                               ("<|startofprev|>", self.sot_prev), ("<|notimestamps|>", self.no_timestamps)):
                 got = self._hf.token_to_id(name)
                 if got != want:
-                    raise ValueError(f"tokenizer.json: {name} is {got}, expected {want} (*.en layout)")
+                    raise ValueError(f"tokenizer.json: {name} is {got}, expected {want} ({layout} layout)")
             ts0 = self._hf.token_to_id("<|0.00|>")
-            if ts0 is not None and ts0 != TIMESTAMP_BEGIN:
-                raise ValueError(f"tokenizer.json: <|0.00|> is {ts0}, expected {TIMESTAMP_BEGIN}")
+            if ts0 is not None and ts0 != self.timestamp_begin:
+                raise ValueError(f"tokenizer.json: <|0.00|> is {ts0}, expected {self.timestamp_begin}")
         else:
-            self._table = self._synthetic_table(seed)
+            self._table = self._synthetic_table(seed, self.eot)
+
+    # ---- language / task tokens
+    def language_token(self, code: str) -> int:
+        """<|code|>'s id; ValueError for a code that is none of the 99."""
+        if not isinstance(code, str) or code not in LANGUAGES:
+            raise ValueError(f"unknown language code {code!r}")
+        return self.language_begin + LANGUAGES.index(code)
+
+    def language_code(self, token: int) -> str:
+        i = int(token) - self.language_begin
+        if not 0 <= i < self.n_languages:
+            raise ValueError(f"token {token} is no language token")
+        return LANGUAGES[i]
+
+    def task_token(self, task: str) -> int:
+        if task not in TASKS:
+            raise ValueError(f"unknown task {task!r}: one of {TASKS}")
+        return self.transcribe if task == "transcribe" else self.translate
+
+    def sot_sequence_for(self, language: str = "en", task: str = "transcribe"):
+        """The start sequence of one utterance: [sot] for ``*.en``, else
+        [sot, <|language|>, <|task|>]. ValueError for an unknown code or task."""
+        lang, tk = self.language_token(language), self.task_token(task)
+        return [self.sot, lang, tk] if self.multilingual else [self.sot]
 
     @staticmethod
-    def _synthetic_table(seed):
+    def _synthetic_table(seed, n=EOT):
+        """ids 0 .. n - 1: the multilingual table (n = 50257) draws the *.en table's words
+        from the same stream and then one more."""
         order = bytes_to_unicode_order()
         table = [bytes([order[k]]) for k in range(256)]
         rng = np.random.default_rng(seed)
         cons = list("bcdfghjklmnprstvwz")
         vows = list("aeiou")
-        for _ in range(256, EOT):
+        for _ in range(256, n):
             n = int(rng.integers(1, 4))
             word = "".join(cons[rng.integers(len(cons))] + vows[rng.integers(len(vows))]
                            for _ in range(n))
@@ -117,12 +176,13 @@ class WhisperTokenizer:
     def suppress_tokens(self):
         """faster-whisper get_suppressed_tokens(tokenizer, [-1])."""
         s = set(self.non_speech_tokens())
-        s.update([TRANSCRIBE, TRANSLATE, SOT, SOT_PREV, SOT_LM])
+        s.update([self.transcribe, self.translate, self.sot, self.sot_prev, self.sot_lm])
         return sorted(s)
 
-    def split_to_word_tokens(self, tokens):
-        """faster-whisper's Tokenizer.split_to_word_tokens for English (split_tokens_on_spaces
-        over split_tokens_on_unicode): (words, word_tokens). First the tokens are cut where
+    def split_to_word_tokens(self, tokens, language=None):
+        """faster-whisper's Tokenizer.split_to_word_tokens (split_tokens_on_spaces over
+        split_tokens_on_unicode; for ``language`` in zh ja th lo my yue, written without
+        spaces, the unicode split alone): (words, word_tokens). First the tokens are cut where
         the incremental decode of the tokens gathered so far holds no U+FFFD (a multi-byte
         character split over tokens stays in one piece) — or holds one that the decode of the
         whole sequence has at the same place, i.e. the text itself carries it (bytes that
@@ -142,6 +202,8 @@ class WhisperTokenizer:
                 piece_tokens.append(cur)
                 cur = []
                 offset += len(text)
+        if language in UNSPACED_LANGUAGES:
+            return pieces, [list(t) for t in piece_tokens]
         words, word_tokens = [], []
         for text, toks in zip(pieces, piece_tokens):
             special = toks[0] >= self.eot
@@ -230,6 +292,6 @@ class WhisperTokenizer:
         return " ".join(texts).strip()
 
 
-def load_tokenizer():
-    return WhisperTokenizer(os.environ.get("JANUS_WHISPER_DIR"))
+def load_tokenizer(multilingual: bool = False):
+    return WhisperTokenizer(os.environ.get("JANUS_WHISPER_DIR"), multilingual=multilingual)
 

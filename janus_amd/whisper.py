@@ -36,6 +36,11 @@ class WhisperConfig:
     def ffn(self):
         return 4 * self.d_model
 
+    @property
+    def multilingual(self) -> bool:
+        """The 51 865-entry vocabulary: language and task tokens, every special id one higher."""
+        return self.n_vocab >= tok.N_VOCAB_MULTILINGUAL
+
 
 CONFIGS = {
     "tiny.en": WhisperConfig("tiny.en", 384, 6, 4, 4),
@@ -43,6 +48,10 @@ CONFIGS = {
     "small.en": WhisperConfig("small.en", 768, 12, 12, 12),
     # distil-whisper: small.en's encoder over a 4-layer decoder
     "distil-small.en": WhisperConfig("distil-small.en", 768, 12, 12, 4),
+    # the multilingual checkpoints: the *.en siblings' shapes over the 51 865-entry vocabulary
+    "tiny": WhisperConfig("tiny", 384, 6, 4, 4, n_vocab=tok.N_VOCAB_MULTILINGUAL),
+    "base": WhisperConfig("base", 512, 8, 6, 6, n_vocab=tok.N_VOCAB_MULTILINGUAL),
+    "small": WhisperConfig("small", 768, 12, 12, 12, n_vocab=tok.N_VOCAB_MULTILINGUAL),
 }
 
 
@@ -98,7 +107,8 @@ class janus_decode_rows(ctypes.Structure):
                 ("prompt_lens", ctypes.POINTER(ctypes.c_int32)),
                 ("stride", ctypes.c_int), ("no_speech_token", ctypes.c_int),
                 ("enc_index", ctypes.POINTER(ctypes.c_int32)), ("n_enc", ctypes.c_int),
-                ("pos_offset", ctypes.POINTER(ctypes.c_int32)), ("steps", ctypes.c_int)]
+                ("pos_offset", ctypes.POINTER(ctypes.c_int32)), ("steps", ctypes.c_int),
+                ("no_speech_back", ctypes.c_int)]
 
 
 # ----------------------------------------------------------------- front end
@@ -345,7 +355,7 @@ class WhisperEngine:
             alignment_heads = check_alignment_heads(cfg, alignment_heads)
         self.device = nat.require_gpu()
         self.cfg = cfg
-        self.tokenizer = tok.load_tokenizer()
+        self.tokenizer = tok.load_tokenizer(multilingual=cfg.multilingual)
         c = janus_whisper_config(cfg.n_mels, cfg.n_audio_ctx, cfg.d_model, cfg.n_heads,
                                  cfg.enc_layers, cfg.dec_layers, cfg.n_vocab, cfg.n_text_ctx)
         h = ctypes.c_void_p()
@@ -467,7 +477,8 @@ class WhisperEngine:
                   check_every: int = 16, timestamps: bool = True, xattn_splits: int = 0,
                   cu_count: int = 0, temperature: float = 0.0, seeds=None, enc_index=None,
                   pos_offset=None, steps: int = 0, state_slot: int = 0, logits_blocks: int = 0,
-                  msplit_rows_n: int = 0, persistent: int = 0, path_flags: int = 0):
+                  msplit_rows_n: int = 0, persistent: int = 0, path_flags: int = 0,
+                  no_speech_back: int = None):
         """janus_whisper_decode_greedy_ex: per-row prompts (lists of token ids; None = the
         SOT sequence for every row) and the no-speech probability. Returns a DecodeOut.
         temperature > 0 samples instead (janus_whisper_decode_sample_ex: Gumbel-max over the
@@ -484,7 +495,10 @@ class WhisperEngine:
         slot); ``logits_blocks`` / ``msplit_rows_n``: launch geometry (0 = measured
         defaults, janus_decode_options); ``persistent``: the persistent decoder segments
         (dec_persist.hip) where the shape allows; ``path_flags``: an alternative decoder path
-        (DEC_PATH_*, parity tests)."""
+        (DEC_PATH_*, parity tests). ``no_speech_back``: no_speech_prob is read that many
+        positions before each prompt's last one (janus_decode_rows.no_speech_back), where the
+        prompt must hold <|startoftranscript|>; None = len(tokenizer.sot_sequence) - 1 (0 on
+        ``*.en``, 2 on a multilingual model)."""
         B = enc.shape[0] if enc_index is None else len(enc_index)
         if steps < 0:
             raise ValueError("steps must be >= 0")
@@ -504,7 +518,7 @@ class WhisperEngine:
                                         state_slot, logits_blocks, msplit_rows_n, persistent,
                                         path_flags)
         rows = janus_decode_rows()
-        rows.no_speech_token = tok.NO_SPEECH
+        rows.no_speech_token = self.tokenizer.no_speech
         po = None
         if pos_offset is not None:
             po = np.ascontiguousarray(np.asarray(pos_offset, np.int32))
@@ -531,6 +545,7 @@ class WhisperEngine:
             rows.prompts = pr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
             rows.prompt_lens = plens.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
             rows.stride = stride
+        rows.no_speech_back = self._no_speech_back(no_speech_back, prompts)
         tokens = torch.empty(B, max_length, dtype=torch.int32, device=self.device)
         ntok = torch.empty(B, dtype=torch.int32, device=self.device)
         slp = torch.empty(B, dtype=torch.float32, device=self.device)
@@ -550,14 +565,14 @@ class WhisperEngine:
                      ctypes.addressof(rows), tokens.data_ptr(), ntok.data_ptr(), slp.data_ptr(),
                      nsp.data_ptr(), nat.stream_ptr())
         del keep, pr, ei, po, row_t
-        return DecodeOut(tokens, ntok, slp, nsp, plens)
+        return DecodeOut(tokens, ntok, slp, nsp, plens, self.tokenizer.eot)
 
     def decode_beam(self, enc: torch.Tensor, prompts=None, beam_size: int = 5,
                     length_penalty: float = 1.0, max_length: int = 448, check_every: int = 16,
                     timestamps: bool = True, xattn_splits: int = 0, cu_count: int = 0,
                     temperature: float = 0.0, pos_offset=None, state_slot: int = 0,
                     logits_blocks: int = 0, msplit_rows_n: int = 0, persistent: int = 0,
-                    path_flags: int = 0):
+                    path_flags: int = 0, no_speech_back: int = None):
         """janus_whisper_decode_beam_ex: beam search at temperature 0 over ``enc``
         [windows][1500][d] (``prompts``: one token list per window; None = the SOT sequence).
         Returns a DecodeOut with one row per window: the winning hypothesis' tokens,
@@ -583,7 +598,7 @@ class WhisperEngine:
                                         state_slot, logits_blocks, msplit_rows_n, persistent,
                                         path_flags)
         rows = janus_decode_rows()
-        rows.no_speech_token = tok.NO_SPEECH
+        rows.no_speech_token = self.tokenizer.no_speech
         plens = np.full(W, len(self.tokenizer.sot_sequence), np.int32)
         pr = None
         if prompts is not None:
@@ -597,6 +612,7 @@ class WhisperEngine:
             rows.prompts = pr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
             rows.prompt_lens = plens.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
             rows.stride = stride
+        rows.no_speech_back = self._no_speech_back(no_speech_back, prompts)
         tokens = torch.empty(W, max_length, dtype=torch.int32, device=self.device)
         ntok = torch.empty(W, dtype=torch.int32, device=self.device)
         slp = torch.empty(W, dtype=torch.float32, device=self.device)
@@ -605,10 +621,41 @@ class WhisperEngine:
                  ctypes.addressof(rows), int(beam_size), ctypes.c_float(length_penalty),
                  tokens.data_ptr(), ntok.data_ptr(), slp.data_ptr(), nsp.data_ptr(), nat.stream_ptr())
         del keep, pr
-        return DecodeOut(tokens, ntok, slp, nsp, plens)
+        return DecodeOut(tokens, ntok, slp, nsp, plens, self.tokenizer.eot)
+
+    def _no_speech_back(self, no_speech_back, prompts) -> int:
+        """janus_decode_rows.no_speech_back of a call: the given value, or where the
+        tokenizer's start sequence puts <|startoftranscript|>; every prompt must hold it
+        there (ValueError otherwise)."""
+        t = self.tokenizer
+        back = len(t.sot_sequence) - 1 if no_speech_back is None else int(no_speech_back)
+        if back < 0:
+            raise ValueError(f"no_speech_back must be >= 0, not {back}")
+        for b, p in enumerate(prompts if prompts is not None else [t.sot_sequence]):
+            if len(p) <= back or int(p[len(p) - 1 - back]) != t.sot:
+                raise ValueError(f"prompt {b}: <|startoftranscript|> ({t.sot}) expected {back} "
+                                 f"tokens before its end (no_speech_back)")
+        return back
+
+    def detect_language(self, enc: torch.Tensor):
+        """janus_whisper_detect_language over ``enc`` [B][1500][d]: (probs f32 [B][n_languages]
+        — the softmax over the language tokens alone of one <|startoftranscript|> position —,
+        best int32 [B], indices into tokenizer LANGUAGES), device tensors (include/janus.h,
+        DESIGN.md §5m). ValueError on an English-only engine."""
+        t = self.tokenizer
+        if not self.cfg.multilingual:
+            raise ValueError(f"detect_language: {self.cfg.name} is English-only")
+        assert enc.dtype == torch.float16 and enc.is_contiguous()
+        B = int(enc.shape[0])
+        probs = torch.empty(B, t.n_languages, dtype=torch.float32, device=self.device)
+        best = torch.empty(B, dtype=torch.int32, device=self.device)
+        nat.call("janus_whisper_detect_language", self._h, enc.data_ptr(), B, int(t.sot),
+                 int(t.language_begin), int(t.n_languages), probs.data_ptr(), best.data_ptr(),
+                 nat.stream_ptr())
+        return probs, best
 
     def align(self, enc: torch.Tensor, texts, sizes, enc_index=None, return_attention: bool = False,
-              phases: int = 0):
+              phases: int = 0, sot_sequences=None):
         """janus_whisper_align: word alignment of several windows in one call. ``texts``: one
         list of text token ids (< eot, the window's segments concatenated) per window;
         ``sizes``: each window's content size in mel frames (2 .. 3000); ``enc_index``: window
@@ -616,16 +663,22 @@ class WhisperEngine:
         for a window without text, which runs nothing): the DTW path over the rows of
         text + [eot] and the frames < size // 2, and the text tokens' forced probabilities
         (include/janus.h rules 1 - 5). ``return_attention`` also returns the
-        matrix A the path was solved on; ``phases``: janus_whisper_align's measurement mask."""
+        matrix A the path was solved on; ``phases``: janus_whisper_align's measurement mask;
+        ``sot_sequences``: one start sequence per window instead of the tokenizer's (a
+        multilingual model's per-utterance language and task)."""
         t = self.tokenizer
         if len(texts) != len(sizes) or (enc_index is not None and len(enc_index) != len(texts)):
             raise ValueError("align: one text, one size (and one enc_index) per window")
         sot = list(t.sot_sequence)
+        # multilingual models: every window's own [sot, <|language|>, <|task|>] (one length)
+        sots = [sot] * len(texts) if sot_sequences is None else [list(q) for q in sot_sequences]
+        if len(sots) != len(texts) or any(len(q) != len(sot) for q in sots):
+            raise ValueError("align: one start sequence of the tokenizer's length per window")
         live = [j for j, x in enumerate(texts) if len(x) > 0]
         out = [None] * len(texts)
         if not live:
             return out
-        seqs = [sot + [t.no_timestamps] + [int(v) for v in texts[j]] + [t.eot] for j in live]
+        seqs = [sots[j] + [t.no_timestamps] + [int(v) for v in texts[j]] + [t.eot] for j in live]
         lens = np.array([len(q) for q in seqs], np.int32)
         if lens.max() > self.cfg.n_text_ctx:
             raise ValueError(f"align: a sequence of {int(lens.max())} tokens exceeds n_text_ctx "
@@ -731,6 +784,7 @@ class DecodeOut:
     sum_logprob: torch.Tensor     # f32 [B]: sum of the chosen tokens' (filtered) log-probs
     no_speech_prob: torch.Tensor  # f32 [B]: raw P(<|nocaptions|>) at the first sampled step
     prompt_lens: np.ndarray       # int32 [B]
+    eot: int = tok.EOT            # the decoding tokenizer's <|endoftext|>
 
     def rows(self):
         """Per row: (sampled tokens without <|endoftext|>, avg_logprob, no_speech_prob),
@@ -740,6 +794,6 @@ class DecodeOut:
         out = []
         for b in range(len(n)):
             s = t[b][int(self.prompt_lens[b]):int(self.prompt_lens[b]) + int(n[b])]
-            s = [int(x) for x in s if x != tok.EOT]
+            s = [int(x) for x in s if x != self.eot]
             out.append((s, float(lp[b]) / (len(s) + 1), float(ns[b])))
         return out
