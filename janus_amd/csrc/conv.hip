@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void conv_kernel(ConvArgs a, int rows_max) {
   _Float16* sIn = smem;
   _Float16* sW = smem + rows_max * LI;  // [2][BN][LW]
 
-  const int nbn = (a.Cout + BN - 1) / BN, nbm = (a.n_rows + BM - 1) / BM;
+  const int nbn = (a.Cout + BN - 1) / BN;
   // tile order (a.remap): 3 = phase-fastest XCD runs (below); 2 = XCD-aware over the whole grid (blocks are dealt to XCDs in
   // linear order, x fastest: each XCD gets a contiguous run of (utterance, phase,
   // row-block) tiles); 1 = over blockIdx.x only; 0 = dispatch order
@@ -366,10 +366,9 @@ void conv_launch(const ConvArgs& args, hipStream_t s) {
   // tile order: phase-fastest XCD runs (3) fetch 1.21x the algorithmic bytes against
   // 1.84x for runs of row blocks per phase (1): the u phases of an upsampler read the same
   // input rows; in the overlapped step 3 costs ~0.9 ms of conv time against 1 (19.9 vs
-  // 19.0 ms), at equal step time. JANUS_CONV_REMAP overrides
-  static const int remap_env = ab_env("JANUS_CONV_REMAP") ? std::atoi(ab_env("JANUS_CONV_REMAP")) : 3;
+  // 19.0 ms), at equal step time.
   ConvArgs a = args;
-  if (a.remap < 0) a.remap = remap_env;
+  if (a.remap < 0) a.remap = 3;
   JANUS_CHECK(a.Cin % 16 == 0, "conv: Cin must be a multiple of 16");
   JANUS_CHECK(a.Cout % 16 == 0, "conv: Cout must be a multiple of 16");
   JANUS_CHECK(a.in_stride >= 1 && a.taps >= 1 && a.phases >= 1, "conv: bad geometry");

@@ -332,15 +332,6 @@ __device__ __forceinline__ void lng_load(half8 (&w)[16], const _Float16* wt, int
   for (int s = 0; s < 16; ++s) w[s] = *reinterpret_cast<const half8*>(wr + 32 * s);
 }
 
-// the wave's first tile of the phase (the rest are loaded during the phase)
-__device__ __forceinline__ void lng_prefetch(LngW& W, const _Float16* wt, int N, int MT,
-                                             int lane, int wv) {
-  int m, nt0, npg;
-  lng_tiles(N, MT, m, nt0, npg);
-  if (wv < npg) lng_load(W.w, wt, nt0 + wv, lane);  // wave-uniform
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 enum LngEpi { LE_F16 = 0, LE_GELU_SC1 = 1, LE_QKV = 2 };
 
 struct LngOut {
@@ -1101,7 +1092,7 @@ __device__ __forceinline__ void xattn_phase(const DecSegArgs& g, float* lds) {
 
 template <bool BIG>
 __global__ __launch_bounds__(kNT, 4) void dec_seg_a_kernel(DecSegArgs a) {
-  JANUS_DEC_WAVE_PRIO();
+  dec_wave_prio();
   extern __shared__ __attribute__((aligned(16))) float seg_smem[];
   long long* st = seg_stamps(a.prof, 0);
   uint32_t touched = 0u, sink = 0u;
@@ -1113,7 +1104,7 @@ __global__ __launch_bounds__(kNT, 4) void dec_seg_a_kernel(DecSegArgs a) {
 
 template <bool BIG>
 __global__ __launch_bounds__(kNT, 4) void dec_seg_b_kernel(DecSegArgs a) {
-  JANUS_DEC_WAVE_PRIO();
+  dec_wave_prio();
   extern __shared__ __attribute__((aligned(16))) float seg_smem[];
   long long* st = seg_stamps(a.prof, 1);
   uint32_t touched = 0u, sink = 0u;
@@ -1128,7 +1119,7 @@ __global__ __launch_bounds__(kNT, 4) void dec_seg_b_kernel(DecSegArgs a) {
 // segment A of layer l + 1 — the launches between two cross-attentions as one grid.
 template <bool BIG>
 __global__ __launch_bounds__(kNT, 4) void dec_layer_kernel(DecSegArgs bsg, DecSegNext nx) {
-  JANUS_DEC_WAVE_PRIO();
+  dec_wave_prio();
   extern __shared__ __attribute__((aligned(16))) float seg_smem[];
   long long* st = seg_stamps(bsg.prof, 2);
   const int lane = threadIdx.x & 63, wv = wave_id();
@@ -1156,7 +1147,7 @@ __global__ __launch_bounds__(kNT, 4) void dec_layer_kernel(DecSegArgs bsg, DecSe
 // launches before the first cross-attention as one grid.
 template <bool BIG>
 __global__ __launch_bounds__(kNT, 4) void dec_head_kernel(DecSegArgs g) {
-  JANUS_DEC_WAVE_PRIO();
+  dec_wave_prio();
   extern __shared__ __attribute__((aligned(16))) float seg_smem[];
   long long* st = seg_stamps(g.prof, 0);
   const int lane = threadIdx.x & 63, wv = wave_id();

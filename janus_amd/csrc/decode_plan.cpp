@@ -56,14 +56,13 @@ static void plan_shared_rows(DecodePlan& P, const janus_whisper_config& c, uint3
     grp_rows = (int)std::min<size_t>((size_t)xrows, maxg);
     // each encoder row's remainder rows (fewer than a full block) go out as blocks of a
     // second launch with their own, smaller m-tile count (a lone row: one m-tile, two blocks
-    // per CU): 5 493 -> 4 496 us per position at 320 rows on small.en, DESIGN.md §5i;
-    // JANUS_XROWS_ONE_LAUNCH (A/B builds) keeps them in the full blocks' launch
-    static const bool split_rem = ab_env("JANUS_XROWS_ONE_LAUNCH") == nullptr;
+    // per CU): 5 493 -> 4 496 us per position at 320 rows on small.en against keeping them
+    // in the full blocks' launch, DESIGN.md §5i
     std::vector<int> rem;
     for (int e = 0; e < n_enc; ++e)
       for (size_t i = 0; i < grp[e].size(); i += grp_rows) {
         const size_t n = std::min<size_t>(grp_rows, grp[e].size() - i);
-        std::vector<int>& dst = (split_rem && (int)n < grp_rows) ? rem : h_groups;
+        std::vector<int>& dst = (int)n < grp_rows ? rem : h_groups;
         if (&dst == &rem) rem_rows = std::max(rem_rows, (int)n);
         dst.push_back(e);
         for (int j = 0; j < 7; ++j) dst.push_back(j < (int)n ? grp[e][i + j] : -1);

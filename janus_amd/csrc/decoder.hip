@@ -386,8 +386,9 @@ int logits_partial_blocks(int V, int K, int max_blocks) {
 // running per-row statistics without shuffles; at the end the 8 waves' statistics are
 // merged per row (wave order) into ONE partial per (row, block) for the selector.
 
-// NB: weight tiles in flight per wave (2: two register sets, the tile two strides ahead is
-// issued after this tile's MFMAs, so each load has two tile-times to land)
+// NB: weight tiles in flight per wave. Every launch uses 1: with 2 (two register sets, the
+// tile two strides ahead issued after this tile's MFMAs) the decoder side measured 303-305
+// vs 302-303 ms per step.
 // SAMPLE (decode at temperature > 0, faster-whisper's fallback): the argmaxes are taken
 // over the perturbed keys logit * inv_temp + Gumbel noise (Gumbel-max: a draw from
 // softmax(logits / T) over the same rule-filtered set), the chosen logit carried beside
@@ -404,7 +405,7 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
     const uint32_t* __restrict__ seeds, int pos, const float* __restrict__ rinv,
     BeamTop* __restrict__ tops) {
   extern __shared__ __attribute__((aligned(16))) _Float16 lg_smem[];
-  JANUS_DEC_WAVE_PRIO();
+  dec_wave_prio();
   // row group blockIdx.y: rows [64 y, 64 y + 64) of the call (one launch for every group:
   // a group's blocks start while the previous group's last blocks drain)
   {
@@ -429,11 +430,6 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
   // do not depend on it); later tiles' loads are issued before the previous epilogue
   half8 bw[NB][NKS];
   uint4 sm16[NB];
-#if defined(JANUS_W_NT) || defined(JANUS_LG_NT)  // A/B: token-embedding stream past the caches
-#define LG_WLD(P) ([&]() { const uint4 u_ = ld_nt(P); return *reinterpret_cast<const half8*>(&u_); }())
-#else
-#define LG_WLD(P) (*reinterpret_cast<const half8*>(P))
-#endif
   // logical tile t -> physical tile (t + rot) mod ntiles (see logits_partial_launch)
   auto phys = [&](int t) { const int q = t + rot; return q >= ntiles ? q - ntiles : q; };
 #define LG_LOAD(BUF, TILE)                                                                    \
@@ -441,7 +437,7 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
     const int bcol_ = min(phys(TILE) * 16 + (lane & 15), V - 1);                              \
     const _Float16* wrow_ = W + (int64_t)bcol_ * K + 8 * (lane >> 4);                         \
     _Pragma("unroll") for (int ks = 0; ks < NKS; ++ks)                                        \
-      bw[BUF][ks] = LG_WLD(wrow_ + 32 * ks);                                                  \
+      bw[BUF][ks] = *reinterpret_cast<const half8*>(wrow_ + 32 * ks);                         \
     /* 16 mask bytes per tile (the mask buffer is padded to a multiple of 16) */             \
     sm16[BUF] = *reinterpret_cast<const uint4*>(smask + phys(TILE) * 16);                     \
   } while (0)
@@ -712,7 +708,6 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
   }
 }
 #undef LG_LOAD
-#undef LG_WLD
 
 void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K, int V, int B,
                            const DecodeRules& R, const uint8_t* smask, const RowRules* rules,
@@ -726,18 +721,14 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
   const int ntiles = (V + 15) / 16;
   const int nw = lg_waves(K);
   const size_t lds = (size_t)64 * (K + 16) * 2 + (size_t)nw * 64 * 17 * 4 + 64 * sizeof(RowRules);
-  // weight tiles in flight per wave (JANUS_LG_DEPTH=2: two)
-  static const int depth = ab_env("JANUS_LG_DEPTH") ? std::atoi(ab_env("JANUS_LG_DEPTH")) : 1;
   auto kern = tops ? (K == 384 ? logits_partial_kernel<12, 1, false, true> : K == 512 ? logits_partial_kernel<16, 1, false, true>
                                                                         : logits_partial_kernel<24, 1, false, true>)
               : sample ? (K == 384 ? logits_partial_kernel<12, 1, true> : K == 512 ? logits_partial_kernel<16, 1, true>
                                                                           : logits_partial_kernel<24, 1, true>)
-              : depth > 1 ? (K == 384 ? logits_partial_kernel<12, 2, false> : K == 512 ? logits_partial_kernel<16, 2, false>
-                                                                            : logits_partial_kernel<24, 1, false>)
-                        : (K == 384 ? logits_partial_kernel<12, 1, false> : K == 512 ? logits_partial_kernel<16, 1, false>
-                                                                            : logits_partial_kernel<24, 1, false>);
-  static bool attr[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
-  const int ai = (K == 384 ? 0 : K == 512 ? 1 : 2) + (tops ? 9 : sample ? 6 : depth > 1 ? 3 : 0);
+                       : (K == 384 ? logits_partial_kernel<12, 1, false> : K == 512 ? logits_partial_kernel<16, 1, false>
+                                                                           : logits_partial_kernel<24, 1, false>);
+  static bool attr[9] = {false, false, false, false, false, false, false, false, false};
+  const int ai = (K == 384 ? 0 : K == 512 ? 1 : 2) + (tops ? 6 : sample ? 3 : 0);
   if (!attr[ai]) {
     JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024));
@@ -750,7 +741,6 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
   // rule-filter epilogue, several times a plain tile's VALU work; rotated so they land in
   // the first round of the waves with one tile fewer. Order-dependent only in the last
   // bits of the softmax sums (the argmax ties break by index either way).
-  static const bool no_rot = ab_env("JANUS_LG_NO_ROT") != nullptr;
   int rot = 0;
   {
     const int stride = grid * nw, rem = ntiles % stride;
@@ -758,7 +748,7 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
     for (int t : {R.eot, R.no_timestamps, R.ts_begin})
       if (t >= 0 && t < V) s0 = std::min(s0, t / 16);
     const int nspec = ntiles - s0;
-    if (!no_rot && rem > 0 && nspec > 0 && rem + nspec + (R.blank >= 0 ? 1 + R.blank / 16 : 0) <= stride)
+    if (rem > 0 && nspec > 0 && rem + nspec + (R.blank >= 0 ? 1 + R.blank / 16 : 0) <= stride)
       rot = ((s0 - rem) % ntiles + ntiles) % ntiles;
   }
   // 64 rows per row group (blockIdx.y), every group in one launch
@@ -782,7 +772,7 @@ __device__ __forceinline__ int select_row(
     float* __restrict__ sum_lp, int32_t* __restrict__ n_tok, const int32_t* __restrict__ plen,
     float* __restrict__ nsp, const int32_t* __restrict__ roff = nullptr) {
   __shared__ LogitPart sh[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = wave_id();
+  const int b = blockIdx.x, tid = threadIdx.x;
   if (roff) {
     pos += roff[b];
     if (pos + 1 >= ld) return -1;  // block-uniform
@@ -851,7 +841,7 @@ __global__ __launch_bounds__(256) void select_embed_kernel(
     int d, float* __restrict__ x, float2* __restrict__ part, const float* __restrict__ ln_g,
     const float* __restrict__ ln_b, _Float16* __restrict__ ln_out, const int32_t* __restrict__ roff) {
   __shared__ int s_tok;
-  JANUS_DEC_WAVE_PRIO();
+  dec_wave_prio();
   const int t = select_row(parts, nblk, R, rules, tokens, ld, pos, done, sum_lp, n_tok, plen, nsp, roff);
   const int pb = pos + (roff ? roff[blockIdx.x] : 0);
   if (pb + 1 >= ld) return;  // a staggered row past its last position: nothing to embed

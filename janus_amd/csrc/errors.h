@@ -1,26 +1,13 @@
 // The error model's host side, free of HIP headers (common.h includes it): the exception
-// type, JANUS_CHECK, the entry-point wrapper and the A/B environment switch.
+// type, JANUS_CHECK and the entry-point wrapper.
 #pragma once
 
-#include <cstdlib>
 #include <stdexcept>
 #include <string>
 
 namespace janus {
 
 void set_error(const std::string& msg);
-
-// Kernel-geometry A/B switches (JANUS_* environment variables) are read only by builds made
-// with -DJANUS_AB_KNOBS (the A/B libraries the tools build beside the product); the product
-// library takes no tuning from the environment and always runs the measured defaults.
-inline const char* ab_env(const char* name) {
-#ifdef JANUS_AB_KNOBS
-  return std::getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
 
 struct Error : std::runtime_error {
   using std::runtime_error::runtime_error;

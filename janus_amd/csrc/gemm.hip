@@ -255,14 +255,7 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(SkinnyArgs p) {
     for (int g = 0; g < G; ++g) {
       const int kk = k0 + 32 * g + kc8;
       const bool ok = kk < kend;
-#ifdef JANUS_W_NT
-      {
-        const uint4 u = (ok && bcol < N) ? ld_nt(wrow + kk) : make_uint4(0, 0, 0, 0);
-        bw[g] = *reinterpret_cast<const half8*>(&u);
-      }
-#else
       bw[g] = (ok && bcol < N) ? *reinterpret_cast<const half8*>(wrow + kk) : zero_half8();
-#endif
 #pragma unroll
       for (int m = 0; m < MTB; ++m) {
         const int r = r0 + m * 16 + lr;
@@ -534,8 +527,7 @@ template <int AM, int EPI, int MTB>
 static void skinny_go(const SkinnyArgs& p, dim3 grid, hipStream_t s) {
   auto kern = gemm_skinny_kernel<EPI, AM, MTB>;
   if constexpr (AM == AM_F16 && MTB == 4) {
-    if (p.K <= kSkWaves * 32 && ab_env("JANUS_SKINNY_NO_K1") == nullptr)
-      kern = gemm_skinny_kernel<EPI, AM, MTB, true>;
+    if (p.K <= kSkWaves * 32) kern = gemm_skinny_kernel<EPI, AM, MTB, true>;
   }
   size_t lds = 0;
   if constexpr (AM == AM_LNX) {
@@ -572,9 +564,8 @@ template <int AM>
 static void launch_skinny_t(int epi, const SkinnyArgs& p, hipStream_t s) {
   // plain fp16 outputs wider than 2048 columns (more 16-column tiles than a 128-CU
   // partition holds in one round) at K <= 512: 32 columns per block
-  static const bool nct2 = ab_env("JANUS_SKINNY_NO_NCT2") == nullptr;
   if constexpr (AM == AM_F16 || AM == AM_LNX) {
-    if (nct2 && epi == EPI_F16 && p.N > 2048 && p.K <= kSkWaves * 32 && p.a_group_cols == 0 && p.M <= 64) {
+    if (epi == EPI_F16 && p.N > 2048 && p.K <= kSkWaves * 32 && p.a_group_cols == 0 && p.M <= 64) {
       if constexpr (AM == AM_LNX) {
         auto kern = gemm_skinny2_kernel<true>;
         static bool attr = false;
@@ -591,13 +582,10 @@ static void launch_skinny_t(int epi, const SkinnyArgs& p, hipStream_t s) {
       return;
     }
   }
-  // narrow outputs (N <= JANUS_SKINNY_MSPLIT_N, default 2048: <= 128 column tiles) split the
-  // rows over 16-row blocks as well, so 4x as many CUs share the latency-bound product
-  static const int msplit_n = [] {
-    const char* e = ab_env("JANUS_SKINNY_MSPLIT_N");
-    return e ? std::atoi(e) : 2048;
-  }();
-  if (p.N <= (p.msplit_n > 0 ? p.msplit_n : msplit_n)) { launch_skinny_m<AM, 1>(epi, p, s); return; }
+  // narrow outputs (N <= msplit_n, default 2048: <= 128 column tiles) split the rows over
+  // 16-row blocks as well, so 4x as many CUs share the latency-bound product
+  constexpr int kMsplitN = 2048;
+  if (p.N <= (p.msplit_n > 0 ? p.msplit_n : kMsplitN)) { launch_skinny_m<AM, 1>(epi, p, s); return; }
   launch_skinny_m<AM, 4>(epi, p, s);
 }
 

@@ -25,7 +25,7 @@ struct GemmArgs {
   // (g+1)*a_group_cols) read A columns [g*K, (g+1)*K) — per-head projections
   int a_group_cols = 0;
   // M <= 64 only: outputs up to this many columns also split their rows over blocks
-  // (0 = JANUS_SKINNY_MSPLIT_N or 2048, tuned on a whole GPU; 1024 on a half-GPU CU mask)
+  // (0 = 2048, tuned on a whole GPU; 1024 on a half-GPU CU mask)
   int msplit_n = 0;
   // a decoder step (rows = decode batch): M <= kSkinnyMaxRows runs on the skinny kernel
   // (rows split over blocks) instead of the 128 x 128 / 256 x 256 tile kernels
@@ -128,16 +128,7 @@ void layernorm_f32_launch(const float* x, const float* g, const float* b, float*
 // (q | k | v, head h at columns h*64), out fp16 [B*T][d].
 void attention_launch(const _Float16* qkv, _Float16* out, int B, int T, int H, float scale,
                       hipStream_t s);
-// One query per (b, h) against Tkv cached keys (decoder self/cross attention).
-// q[b*q_bs + h*64 + d]; k/v[b*kv_bs + t*kv_rs + h*64 + d]; out[b*o_bs + h*64 + d].
-// tkv: device int32 per batch row (NULL => Tkv for all).
-void decode_attention_launch(const _Float16* q, int64_t q_bs, const _Float16* k, const _Float16* v,
-                             int64_t kv_bs, int64_t kv_rs, int Tkv, const int32_t* tkv,
-                             _Float16* out, int64_t o_bs, int B, int H, float scale,
-                             hipStream_t s);
 
-// Split-key (flash-decoding) variant for d <= 512: all heads of a row per block.
-// part_o: f32 [B][splits][d], part_ml: f32 [B][splits][H][2] workspaces.
 // Decoder cross-attention over the encoder output with absorbed K/V projections
 // (xattn.hip). xattn_absorb builds Wqk [H*D][D] fp16 and bqk [H*D] f32 (scores in the
 // exp2 domain) from the fp32 q/k projections; xattn_launch takes qk [B][H*D] fp16 and
@@ -179,6 +170,10 @@ void xattn_combine_vproj_launch(const float* part_c, const float* part_ml, int n
                                 int D, const _Float16* wv, const float* bv, _Float16* out, int64_t ldo,
                                 hipStream_t s);
 
+// One query per (b, h) against Tkv cached keys (decoder self-attention).
+// q[b*q_bs + h*64 + d]; k/v[b*kv_bs + t*kv_rs + h*64 + d]; out[b*o_bs + h*64 + d].
+// Up to 512 keys: one block per (head, row). More: split-key (flash-decoding) for d <= 512,
+// all heads of a row per block; part_o: f32 [B][splits][d], part_ml: f32 [B][splits][H][2].
 int decode_split_count(int Tkv);
 void decode_attention_split_launch(const _Float16* q, int64_t q_bs, const _Float16* k,
                                    const _Float16* v, int64_t kv_bs, int64_t kv_rs, int Tkv,

@@ -15,7 +15,7 @@
 
 namespace janus {
 
-constexpr int kNfft = 400, kHop = 160, kBins = 201;
+constexpr int kNfft = 400, kHop = 160;
 constexpr int kBinPad = 208;                 // 13 tiles of 16
 constexpr int kNB = 2 * kBinPad;             // basis columns: cos | sin
 constexpr int kMels = 80;

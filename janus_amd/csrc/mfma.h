@@ -71,11 +71,8 @@ __device__ __forceinline__ float xshfl(float v) {
 // priority 0, so the latency-bound decoder phases win the issue arbitration on a shared
 // SIMD and YIN takes the cycles they leave (decoder side -4 to -5 ms per step at the same
 // YIN share; with a sixth packet of vocoder work moved to it, 241.4-241.7 vs 243.6-244.0 ms
-// per step, profiles/r05_dec_prio_ab.txt). -DJANUS_DEC_PRIO=0 builds the old order.
-#ifndef JANUS_DEC_PRIO
-#define JANUS_DEC_PRIO 3
-#endif
-#define JANUS_DEC_WAVE_PRIO() __builtin_amdgcn_s_setprio(JANUS_DEC_PRIO)
+// per step, profiles/r05_dec_prio_ab.txt).
+__device__ __forceinline__ void dec_wave_prio() { __builtin_amdgcn_s_setprio(3); }
 
 template <int O>
 __device__ __forceinline__ int xshfl_i(int v) {
@@ -99,27 +96,18 @@ __device__ __forceinline__ float silu(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x));
 }
 
-// SiLU of 8 staged fp16 activations. Default: each through fp32 (silu above) and rounded
-// once. JANUS_SILU_F16: fp16 arithmetic (v_exp_f16 / v_rcp_f16, packed multiplies), no
-// conversions — a few fp16 ulps instead of half of one.
+// SiLU of 8 staged fp16 activations: each through fp32 (silu above) and rounded once (fp16
+// arithmetic, v_exp_f16 / v_rcp_f16, costs a few fp16 ulps instead of half of one).
 __device__ __forceinline__ half8 silu_h8(half8 v) {
-#ifdef JANUS_SILU_F16
-  const half8 t = v * (_Float16)(-1.4426950408889634f);
-  half8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = __builtin_amdgcn_rcph((_Float16)1.0f + __builtin_elementwise_exp2(t[j]));
-  return v * r;
-#else
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = (_Float16)silu((float)v[j]);
   return v;
-#endif
 }
 
 // Streaming activation traffic of the vocoder (tiles read once per unit, outputs written
-// once): with JANUS_ACT_NT the accesses carry the non-temporal hint, so the multi-GB
-// vocoder stream does not displace what the concurrently running decoder re-reads
-// (encoder output, weights) from the caches.
+// once): the accesses carry the non-temporal hint, so the multi-GB vocoder stream does not
+// displace what the concurrently running decoder re-reads (encoder output, weights) from
+// the caches.
 // Measured (overlapped bench step, r02): non-temporal OUTPUT stores — 324.3 -> 319.3 ms,
 // both sides faster (decoder -5.5 ms: its re-read encoder output and weights survive in
 // the caches; vocoder -3 ms); non-temporal loads as well then cost the vocoder +4.5 ms
@@ -128,83 +116,25 @@ __device__ __forceinline__ half8 silu_h8(half8 v) {
 // activation access is non-temporal by default: decoder side 278.4 -> 275.7 ms, vocoder
 // side +2 ms, step 289.6-290.7 -> 287.2-287.9 ms (A/B on one box; the staging loads alone
 // change nothing, the gain is the residual / accumulator re-reads).
-// Switches for A/B builds: JANUS_ACT_LD_PLAIN (plain loads), or JANUS_ACT_NT_LD /
-// JANUS_ACT_NT_RES alone (tile staging loads / epilogue re-reads); JANUS_ACT_ST_PLAIN
-// (plain stores).
-#ifndef JANUS_ACT_LD_PLAIN
-#ifndef JANUS_ACT_NT_LD
-#define JANUS_ACT_NT_LD
-#endif
-#ifndef JANUS_ACT_NT_RES
-#define JANUS_ACT_NT_RES
-#endif
-#endif
-#ifndef JANUS_ACT_ST_PLAIN
-#define JANUS_ACT_NT_ST
-#endif
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld_nt(const _Float16* p) {
   const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
   return make_uint4(v.x, v.y, v.z, v.w);
 }
-__device__ __forceinline__ uint4 ld_act(const _Float16* p) {  // tile staging
-#ifdef JANUS_ACT_NT_LD
-  return ld_nt(p);
-#else
-  return *reinterpret_cast<const uint4*>(p);
-#endif
-}
-// Tile staging with the halo rows a neighbouring tile re-reads kept in L2 (r04): a row read
-// by two tiles (the (k-1)d + halo-recompute rows at either end of a tile's window) is
-// loaded with the default policy so the neighbour (same XCD: tile_remap) finds it in L2;
-// rows only this tile reads stay non-temporal. `keep` must be wave-uniform (one load form
-// per wave, no exec-masked pair). JANUS_HALO_NT: every staging load non-temporal (r03).
-// Default since r04 (staggered step): the C = 64 / 32 callers keep EVERY staged row (their
-// epilogues re-read the body rows as the residual): traffic 1.26 / 1.36x -> 1.00 / 1.00x of
-// the algorithmic bytes, step level-to-better in two same-box pairs (266.2 / 266.9 vs 266.6
-// / 267.7 ms). JANUS_STAGE_HALO_ONLY (A/B build): only the halo rows kept, as r04 v2.
-#ifdef JANUS_STAGE_HALO_ONLY
-#define JANUS_STAGE_KEEP_ALL 0
-#else
-#define JANUS_STAGE_KEEP_ALL 1
-#endif
+__device__ __forceinline__ uint4 ld_act(const _Float16* p) { return ld_nt(p); }  // tile staging
+// Tile staging of the C = 64 / 32 units, `keep`: the row is loaded with the default policy
+// and stays in L2, where the neighbouring tile (same XCD: xcd_remap) finds the halo rows it
+// re-reads and this tile's epilogue the body rows it re-reads as the residual; else
+// non-temporal. Keeping every staged row (r04, staggered step): traffic 1.26 / 1.36x ->
+// 1.00 / 1.00x of the algorithmic bytes, step level-to-better in two same-box pairs (266.2 /
+// 266.9 vs 266.6 / 267.7 ms) against keeping only the halo rows (r04 v2).
 __device__ __forceinline__ uint4 ld_act_halo(const _Float16* p, bool keep) {
-#if defined(JANUS_ACT_NT_LD) && !defined(JANUS_HALO_NT)
   if (keep) return *reinterpret_cast<const uint4*>(p);
   return ld_nt(p);
-#else
-  (void)keep;
-  return ld_act(p);
-#endif
 }
-__device__ __forceinline__ uint4 ld_res(const _Float16* p) {  // epilogue re-reads
-#ifdef JANUS_ACT_NT_RES
-  return ld_nt(p);
-#else
-  return *reinterpret_cast<const uint4*>(p);
-#endif
-}
-// Write-through (sc1) vector stores: the line leaves the XCD's L2 with the store, so no
-// dirty vocoder line is left for a kernel-boundary L2 writeback to flush (the greedy
-// decoder beside the vocoder shares every XCD's L2 and ends ~68 kernels per position).
-// Plain / nt stores KEEP the line dirty in L2 (MI355X_MICROARCH.md, store flavours).
-// Inline asm: hipcc counts no asm store; s_endpgm waits for them, and nothing in the
-// kernel re-reads a stored activation.
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void st_wt16(void* p, u32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void st_wt8(void* p, u32x2 v) {
-  asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
+__device__ __forceinline__ uint4 ld_res(const _Float16* p) { return ld_nt(p); }  // epilogue re-reads
 __device__ __forceinline__ void st_act(_Float16* p, const half8& v) {
-#if defined(JANUS_ACT_WT)
-  st_wt16(p, __builtin_bit_cast(u32x4, v));
-#elif defined(JANUS_ACT_NT_ST)
   __builtin_nontemporal_store(v, reinterpret_cast<half8*>(p));
-#else
-  *reinterpret_cast<half8*>(p) = v;
-#endif
 }
 
 __device__ __forceinline__ half8 zero_half8() {
@@ -242,48 +172,18 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-// The vocoder kernels' tile order (JANUS_NO_TILE_REMAP: plain dispatch order, for A/B
-// builds). Remapped, the standalone vocoder's L2->fabric traffic fell from 1.42x to
-// 1.19x the algorithmic bytes (profiles/traffic_r02.json).
-__device__ __forceinline__ int tile_remap(int bid, int nblocks) {
-#ifdef JANUS_NO_TILE_REMAP
-  return bid;
-#else
-  return xcd_remap(bid, nblocks);
-#endif
-}
+// The vocoder kernels take their tiles in this order: against plain dispatch order the
+// standalone vocoder's L2->fabric traffic fell from 1.42x to 1.19x the algorithmic bytes
+// (profiles/traffic_r02.json).
 
 // Store an MFMA output fragment (lane = column col = tile column (lane & 15), rows row0 + rr,
-// rr < 4, row0 = m*16 + 4*(lane >> 4)) as fp16 into an LDS tile with 4-byte stores: lanes
-// l and l^1 trade two packed halves (one DPP quad_perm move), then the even lane writes rows
-// 0-1 and the odd lane rows 2-3 of the column pair (col & ~1, col | 1): half the store
-// instructions of per-element 2-byte stores. Opt-in build switch JANUS_C1_PAIRS: measured
-// slower (standalone 64 x 30 s vocoder 154.0 vs 151.9 ms), so the LDS bank conflicts of
-// the wide units do not come from these stores; the default is the 2-byte form.
-__device__ __forceinline__ void st_frag_f16_pairs(_Float16* tile, int ld, int row0, int col,
-                                                  const float (&v)[4], int lane) {
-#ifndef JANUS_C1_PAIRS
+// rr < 4, row0 = m*16 + 4*(lane >> 4)) as fp16 into an LDS tile, one 2-byte store per
+// element. Trading halves with lane l^1 (one DPP move) for 4-byte stores measured slower
+// (standalone 64 x 30 s vocoder 154.0 vs 151.9 ms), so the LDS bank conflicts of the wide
+// units do not come from these stores.
+__device__ __forceinline__ void st_frag_f16(_Float16* tile, int ld, int row0, int col, const float (&v)[4]) {
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) tile[(row0 + rr) * ld + col] = (_Float16)v[rr];
-#else
-  const bool odd = lane & 1;
-  const half2v mine_lo = {(_Float16)v[0], (_Float16)v[1]}, mine_hi = {(_Float16)v[2], (_Float16)v[3]};
-  const half2v send = odd ? mine_lo : mine_hi;
-  const int got_i = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), 0xB1 /* quad_perm [1,0,3,2] */,
-                                                0xF, 0xF, false);
-  const half2v got = __builtin_bit_cast(half2v, got_i);
-  half2v ra, rb;
-  if (odd) {  // rows 2, 3: (partner's column, mine)
-    ra = half2v{got[0], mine_hi[0]};
-    rb = half2v{got[1], mine_hi[1]};
-  } else {    // rows 0, 1: (mine, partner's column)
-    ra = half2v{mine_lo[0], got[0]};
-    rb = half2v{mine_lo[1], got[1]};
-  }
-  const int r = row0 + (odd ? 2 : 0), c0 = col & ~1;
-  *reinterpret_cast<half2v*>(tile + r * ld + c0) = ra;
-  *reinterpret_cast<half2v*>(tile + (r + 1) * ld + c0) = rb;
-#endif
 }
 
 // LayerNorm arithmetic shared by layernorm_kernel and resid_ln_kernel (gemm.hip), written

@@ -31,9 +31,8 @@ namespace janus {
 constexpr int kYinBuf = 4096;          // aubio pitch buffer (prosody.py:32)
 constexpr int kYinLen = kYinBuf / 2;   // yin fvec length
 // Block = NT threads, each lane owns 2 consecutive taus, so one pass covers 2·NT taus.
-// NT = 128 (256-tau passes, the default for an uncapped grid): a voiced hop stops within
-// 256 taus of its period; NT = 64 / 256 (128- / 512-tau passes) by JANUS_YIN_THREADS; 256
-// for a grid capped beside the decoder.
+// NT = 128 (256-tau passes) for an uncapped grid: a voiced hop stops within 256 taus of its
+// period; NT = 256 (512-tau passes) for a grid capped beside the decoder.
 
 __device__ __forceinline__ int find_utt(const int64_t* offs, int B, int64_t g) {
   // largest b with offs[b] <= g (offs is non-decreasing, offs[0]=0, offs[B]=total)
@@ -90,11 +89,7 @@ __global__ __launch_bounds__(kYinThreads) void yin_hops_kernel(
         const bool in_pcm = p >= 0 && p < n;
         const bool in_st = p < 0 && st != nullptr;
         const float* src = in_pcm ? pcm + base + p : (in_st ? st + kYinBuf + p : pcm);
-#ifdef JANUS_YIN_NT  // A/B: the window stream past the caches (YIN runs beside the decoder)
-        v[u] = __builtin_nontemporal_load(src);
-#else
         v[u] = *src;
-#endif
         v[u] = (in_pcm || in_st) ? v[u] : 0.0f;
       }
 #pragma unroll
@@ -555,14 +550,8 @@ void prosody_launch(const float* pcm, const int64_t* sample_off, const int64_t* 
     // standalone, 302.0-302.2 vs 304.7-305.1 ms per step; with the scalar loop one-wave
     // blocks had been 1.6 ms per step faster); a capped grid beside the greedy decoder
     // keeps the 256-thread blocks (back-to-back step: 422 vs 449 ms per step with 128)
-    static const int nt_env = ab_env("JANUS_YIN_THREADS") ? std::atoi(ab_env("JANUS_YIN_THREADS")) : 0;
-    const int nt = nt_env > 0 ? nt_env : (max_blocks > 0 ? 256 : 128);
-    if (nt == 256)
+    if (max_blocks > 0)
       yin_hops_kernel<256><<<dim3((unsigned)grid), dim3(256), 0, stream>>>(
-          pcm, sample_off, hop_off, B, hop, state_in, tol, silence_db, level_thr, (unsigned)sample_rate,
-          f0_out, total_hops);
-    else if (nt == 64)  // 128-tau passes
-      yin_hops_kernel<64><<<dim3((unsigned)grid), dim3(64), 0, stream>>>(
           pcm, sample_off, hop_off, B, hop, state_in, tol, silence_db, level_thr, (unsigned)sample_rate,
           f0_out, total_hops);
     else

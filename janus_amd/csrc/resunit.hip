@@ -10,7 +10,6 @@
 // matrices stay in LDS for the block. HBM traffic per unit: read x once (+ the residual
 // re-read, L2-hot), write out once — half of two separate conv launches.
 #include <algorithm>
-#include <cstdlib>
 #include "mfma.h"
 #include "kernels.h"
 
@@ -45,7 +44,7 @@ void resunit_pack(const float* w, _Float16* out, int C, int k, hipStream_t s) {
 // c1 covers M1 = BM + 16 rows (>= BM + K - 1, c2's halo); a 16x16x32 MFMA k-step spans
 // TPK = 32 / C taps, so K rounds up to TP taps with zero weights on the padding tap;
 // every row a padding tap touches is staged (and finite), so the MFMA loop has no guards.
-template <int C, int K, int D, int BM, int NW = 4>
+template <int C, int K, int D, int BM, int NW>
 struct NarrowGeo {
   static constexpr int NT = 64 * NW;                    // NW waves per block
   static constexpr int TPK = 32 / C;                    // taps per k-step
@@ -67,12 +66,8 @@ struct NarrowGeo {
   // epilogue passes: at C = 32 the fp32 tile goes out in two row halves so that the
   // block fits in 80 KB of LDS (two blocks per CU)
   // (C = 16 too: the half-size fp32 tile brings its block to 31 KB of LDS, four blocks
-  // per CU instead of three; JANUS_NARROW16_NP=1 builds the single-pass form)
-#ifndef JANUS_NARROW16_NP
-#define JANUS_NARROW16_NP 2
-#endif
-  static constexpr int NP =
-      C == 32 ? 2 : (NE % JANUS_NARROW16_NP == 0 && MW2 % JANUS_NARROW16_NP == 0 ? JANUS_NARROW16_NP : 1);
+  // per CU instead of the single-pass form's three)
+  static constexpr int NP = C == 32 ? 2 : (NE % 2 == 0 && MW2 % 2 == 0 ? 2 : 1);
   static constexpr int RP = 16 * NW * (MW2 / NP);       // rows per epilogue pass
   // the residual x rows: kept from the staging in an LDS tile where LDS allows (C = 16),
   // else re-read from global memory (L2-hot) into registers during the convs
@@ -134,11 +129,8 @@ __global__ __launch_bounds__(64 * NW) void resunit_kernel(ResUnitArgs a, int til
       const int idx = tid + i * NT;                                                         \
       const int r = idx / CPR, cc = idx % CPR;                                              \
       const int t = t0_ - P2 - P1 + r;                                                      \
-      const int rw_ = w * (64 / CPR) + i * (NT / CPR);                                      \
       pf[i] = (L_ < n_tiles && r < R0  && t >= 0 && t < T)                                 \
-                  ? ld_act_halo(xb_ + (int64_t)t * C + cc * 8,                              \
-                                C == 32 && (JANUS_STAGE_KEEP_ALL || rw_ < R0 - BM ||        \
-                                            rw_ + 64 / CPR > BM))                           \
+                  ? ld_act_halo(xb_ + (int64_t)t * C + cc * 8, C == 32)                     \
                   : make_uint4(0, 0, 0, 0);                                                 \
     }                                                                                       \
   } while (0)
@@ -149,7 +141,7 @@ __global__ __launch_bounds__(64 * NW) void resunit_kernel(ResUnitArgs a, int til
   // compiled with the remap ran 2 ms per step slower, remapped or not)
   const bool xm = C == 32 && (gridDim.x & 7) == 0;
   auto tile_of = [=](int L) {
-    if constexpr (C == 32) return xm ? tile_remap(L, n_tiles) : L;
+    if constexpr (C == 32) return xm ? xcd_remap(L, n_tiles) : L;
     else return L;
   };
   NARROW_PREFETCH(blockIdx.x);
@@ -255,7 +247,7 @@ __global__ __launch_bounds__(64 * NW) void resunit_kernel(ResUnitArgs a, int til
               v[rr] = (t >= 0 && t < T) ? v[rr] : 0.0f;
             }
           }
-          st_frag_f16_pairs(sS, LI, m * 16 + 4 * (lane >> 4), co, v, lane);
+          st_frag_f16(sS, LI, m * 16 + 4 * (lane >> 4), co, v);
         }
       }
     }
@@ -351,39 +343,24 @@ static void narrow_cfg(const ResUnitArgs& a, hipStream_t s) {
   // eight rounds of short tile stripes, which balances the uneven tile costs (edge tiles,
   // HBM contention with the decoder) better than fewer, longer stripes. Sweep (vocoder
   // side per step): 128 -> +3 ms, 256 -> 315.6, 512 -> 313.5, 1024 -> 312.2, 2048 -> 313,
-  // one block per tile -> 327.7 ms. JANUS_NARROW_GRID_CUS overrides the 1024.
-  static const int gcu = ab_env("JANUS_NARROW_GRID_CUS") ? std::atoi(ab_env("JANUS_NARROW_GRID_CUS")) : 1024;
-  const int grid = std::min(n_tiles, std::max(1, gcu) * per_cu);
+  // one block per tile -> 327.7 ms.
+  const int grid = std::min(n_tiles, 1024 * per_cu);
   kern<<<grid, G::NT, G::LDS, s>>>(a, tiles_per_utt, n_tiles);
   JANUS_LAUNCH_CHECK();
 }
 
-#ifndef JANUS_NARROW16_BM
-#define JANUS_NARROW16_BM 240
-#endif
-#ifndef JANUS_NARROW32_BM
-#define JANUS_NARROW32_BM 240
-#endif
-template <int C, int K, int NW>
-static void narrow_dw(const ResUnitArgs& a, hipStream_t s) {
-  constexpr int BM = C == 16 ? JANUS_NARROW16_BM : JANUS_NARROW32_BM;  // output rows per tile
+// waves per block: C = 32 runs 8 waves: its blocks (76 KB of LDS, 2 per CU) gave each SIMD
+// only 2 waves to hide the staging, SiLU and epilogue phases behind the other block's MFMAs
+// (overlapped step: C = 32 units 39.7 -> 34.0 ms against 4 waves); C = 16 (3 blocks per CU
+// already) is level-to-slower at 8 (29.9 -> 30.4 ms) and runs 4.
+template <int C, int K>
+static void narrow_d(const ResUnitArgs& a, hipStream_t s) {
+  constexpr int BM = 240;  // output rows per tile
+  constexpr int NW = C == 32 ? 8 : 4;
   if (a.d == 1) narrow_cfg<C, K, 1, BM, NW>(a, s);
   else if (a.d == 3) narrow_cfg<C, K, 3, BM, NW>(a, s);
   else if (a.d == 5) narrow_cfg<C, K, 5, BM, NW>(a, s);
   else throw Error("resunit: dilation must be 1, 3 or 5");
-}
-
-// waves per block (JANUS_NARROW_WAVES: 4 or 8). C = 32 runs 8 waves: its blocks (76 KB of
-// LDS, 2 per CU) gave each SIMD only 2 waves to hide the staging, SiLU and epilogue phases
-// behind the other block's MFMAs (overlapped step: C = 32 units 39.7 -> 34.0 ms); C = 16
-// (3 blocks per CU already) is level-to-slower at 8 (29.9 -> 30.4 ms).
-template <int C, int K>
-static void narrow_d(const ResUnitArgs& a, hipStream_t s) {
-  static const int nw = ab_env("JANUS_NARROW_WAVES") ? std::atoi(ab_env("JANUS_NARROW_WAVES"))
-                                                          : (C == 32 ? 8 : 4);
-  if constexpr (C == 16 && JANUS_NARROW16_BM != 240) narrow_dw<C, K, 4>(a, s);  // BM A/B builds
-  else if (nw == 8) narrow_dw<C, K, 8>(a, s);
-  else narrow_dw<C, K, 4>(a, s);
 }
 
 template <int C>

@@ -28,7 +28,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <string>
 #include <type_traits>
 #include "mfma.h"
 #include "kernels.h"
@@ -61,43 +60,25 @@ __global__ void resunit_wide_pack_kernel(const float* __restrict__ w, _Float16* 
 #define JANUS_PROF(I) do { } while (0)
 #endif
 
-#ifdef JANUS_ABL_NOSILU  // timing ablation only (wrong results)
-#define WSILU(x) (x)
-#else
-#define WSILU(x) silu(x)
-#endif
-
-template <int C, int V = 0> struct WideCfg;
+template <int C> struct WideCfg;
 // BM output rows per block, WM x WN waves (wave tile: every WM-th m-tile x C/WN columns),
 // NPB = weight k-steps in flight per wave (divides the k-step count k*C/32).
-// EPF: residual / accumulator rows loaded before c2 (in flight during it) where the
-// registers allow, else after it.
 // NP: epilogue passes (the fp32 tile in NP row slices so the block fits 3 per CU)
-template <> struct WideCfg<128> { static constexpr int BM = 112, WM = 1, WN = 4, NPB = 4, NP = 2; static constexpr bool EPF = false, AROT = false; };
-// 8 waves (2 x 4): half the m-tiles per wave, so fewer registers per wave and two 8-wave
-// blocks per CU (16 waves) instead of three 4-wave blocks (JANUS_WIDE128_CFG=1).
-// Measured slower (64 x 30 s, whole GPU: C = 128 units 47.5 -> 59.6 ms): each weight
-// fragment is now fetched by two waves; kept as an A/B switch.
-// ring depth 2 (the default, JANUS_WIDE128_CFG=2): 16 fewer VGPRs, three blocks per CU
-template <> struct WideCfg<128, 2> { static constexpr int BM = 112, WM = 1, WN = 4, NPB = 2, NP = 2; static constexpr bool EPF = false, AROT = true; };
-template <> struct WideCfg<128, 1> { static constexpr int BM = 112, WM = 2, WN = 4, NPB = 4, NP = 1; static constexpr bool EPF = false, AROT = false; };
-// C = 256 on the register ring (JANUS_WIDE256_CFG=ring): 8 waves x 32 columns over all
-// m-tiles, weights from L2 into registers. Per block k-step: A-fragment LDS reads 64 KB
-// (512 clocks at 128 B/clock), weight fragments 16 KB over the L1 path (256 clocks), MFMA
-// 512 clocks per SIMD — against the LDS-staged form's 80 KB of LDS traffic (640 clocks).
-template <> struct WideCfg<256, 3> { static constexpr int BM = 112, WM = 1, WN = 8, NPB = 2, NP = 2; static constexpr bool EPF = false, AROT = false; };
-// C = 64 on the register ring (JANUS_WIDE64_CFG=ring): 2 x 2 waves of 32 columns x 6
-// m-tiles; per block k-step A-fragment LDS reads 24 KB and weight fragments 8 KB from L2
-// (three blocks per CU: 576 / 384 clocks against 576 of MFMA), where the LDS-staged form
-// moves 32 KB through LDS (768 clocks). Measured slower all the same (standalone 64 x 30 s,
-// C = 64 units 30.9-31.1 vs 30.2 ms): kept as an A/B switch.
-template <> struct WideCfg<64, 5> { static constexpr int BM = 176, WM = 2, WN = 2, NPB = 2, NP = 1; static constexpr bool EPF = false, AROT = false; };
-// the same with the weight ring 4 deep (the default; one block per CU either way)
-template <> struct WideCfg<256, 4> { static constexpr int BM = 112, WM = 1, WN = 8, NPB = 4, NP = 2; static constexpr bool EPF = false, AROT = false; };
+// C = 128: 4 waves, weight ring 2 deep (166 VGPRs, three blocks per CU). Standalone 64 x 30 s,
+// C = 128 units: 45.4 ms, against 49.0 (ring 4 deep: 178 VGPRs, two blocks) and 59.6 (8 waves,
+// 2 x 4: each weight fragment fetched by two waves).
+template <> struct WideCfg<128> { static constexpr int BM = 112, WM = 1, WN = 4, NPB = 2, NP = 2; static constexpr bool AROT = true; };
+// C = 256: 8 waves x 32 columns over all m-tiles, weights from L2 into registers, ring 4 deep
+// (one block per CU). Per block k-step: A-fragment LDS reads 64 KB (512 clocks at
+// 128 B/clock), weight fragments 16 KB over the L1 path (256 clocks), MFMA 512 clocks per
+// SIMD — against the LDS-staged form's 80 KB of LDS traffic (640 clocks). Standalone
+// 64 x 30 s, C = 256 units 27.0 (LDS-staged) -> 22.3 ms (22.8 with the ring 2 deep);
+// overlapped step, vocoder side 289 -> 282 ms.
+template <> struct WideCfg<256> { static constexpr int BM = 112, WM = 1, WN = 8, NPB = 4, NP = 2; static constexpr bool AROT = false; };
 
-template <int C, int V = 0>
+template <int C>
 struct WideGeo {
-  using Cfg = WideCfg<C, V>;
+  using Cfg = WideCfg<C>;
   static constexpr int BM = Cfg::BM, WM = Cfg::WM, WN = Cfg::WN, NPB = Cfg::NPB;
   static constexpr int NW = WM * WN, NT = NW * 64;
   static constexpr int LI = frag_pitch(C);        // activation row pitch (halves)
@@ -116,7 +97,7 @@ struct WideGeo {
   static constexpr int ACT = std::max(R0MAX * LI, MT1 * 16 * LI);
   static constexpr size_t LDS = std::max((size_t)ACT * 2, (size_t)RP * ES * 4);
   // blocks per CU the register budget is sized for (C = 256: one 8-wave block, 256 VGPRs)
-  static constexpr int MINB = C == 256 ? 1 : (C == 64 || Cfg::NPB == 2 ? 3 : 2);
+  static constexpr int MINB = C == 256 ? 1 : 3;
   static_assert(BM % 16 == 0 && C % (16 * WN) == 0 && C % 32 == 0, "tiling");
 };
 
@@ -254,11 +235,11 @@ __device__ __forceinline__ void wide_conv(f32x4 (&acc)[MW][G::NTW], const _Float
 // mapping: those slots stay in registers through c1 and c2 (raw x; the LDS tile holds
 // silu(x)) instead of being re-read from HBM after c2 (the 1.4-1.6x traffic of the
 // re-reading form). KC = 0: (k, d) at run time, residual re-read after c2.
-template <int C, int V, int KC = 0, int DC = 0>
-__global__ __launch_bounds__((WideGeo<C, V>::NT), (WideGeo<C, V>::MINB)) void resunit_wide_kernel(ResUnitArgs a,
+template <int C, int KC = 0, int DC = 0>
+__global__ __launch_bounds__((WideGeo<C>::NT), (WideGeo<C>::MINB)) void resunit_wide_kernel(ResUnitArgs a,
                                                                          int tiles_per_utt,
                                                                          long long* prof) {
-  using G = WideGeo<C, V>;
+  using G = WideGeo<C>;
   constexpr int BM = G::BM, WM = G::WM, NT = G::NT, LI = G::LI;
   constexpr int CPR = G::CPR, MT1 = G::MT1, MT2 = G::MT2, MW1 = G::MW1, MW2 = G::MW2;
   constexpr int NTW = G::NTW, ES = G::ES;
@@ -283,7 +264,7 @@ __global__ __launch_bounds__((WideGeo<C, V>::NT), (WideGeo<C, V>::MINB)) void re
   const int R0 = MT1 * 16 + (k - 1) * d;       // x rows c1 reads
   // consecutive tiles on one XCD: a tile's halo rows are its neighbour's, staged through
   // the same L2
-  const int tile = tile_remap(blockIdx.x, gridDim.x);
+  const int tile = xcd_remap(blockIdx.x, gridDim.x);
   const int b = tile / tiles_per_utt, t0 = (tile % tiles_per_utt) * BM;
   const int tid = threadIdx.x, lane = tid & 63, wid = wave_id();
   const int wm = wid % WM, wn = wid / WM;
@@ -312,11 +293,7 @@ __global__ __launch_bounds__((WideGeo<C, V>::NT), (WideGeo<C, V>::MINB)) void re
       const int rl = (ILO + i) * RPI + rr0;  // row relative to t0
       const int t = t0 + rl;
       const int tc = min(max(t, 0), T - 1);
-#ifdef JANUS_ABL_NOSTAGE  // timing ablation only (wrong results)
-      pf[i] = make_uint4(tc, 0, 0, 0);
-#else
       pf[i] = ld_act(xb + (int64_t)tc * C + cc * 8);
-#endif
       if (!(rl >= -P && rl < R0C - P && t >= 0 && t < T)) pf[i] = make_uint4(0, 0, 0, 0);
     }
 #pragma unroll
@@ -324,12 +301,7 @@ __global__ __launch_bounds__((WideGeo<C, V>::NT), (WideGeo<C, V>::MINB)) void re
       const int rl = (ILO + i) * RPI + rr0;
       if (rl >= -P && rl < R0C - P) {
         half8 v = *reinterpret_cast<const half8*>(&pf[i]);
-#ifdef JANUS_ABL_NOSILU
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (_Float16)WSILU((float)v[j]);
-#else
         v = silu_h8(v);
-#endif
         *reinterpret_cast<half8*>(sX + (rl + P) * LI + cc * 8) = v;
       }
     }
@@ -345,11 +317,7 @@ __global__ __launch_bounds__((WideGeo<C, V>::NT), (WideGeo<C, V>::MINB)) void re
       const int t = xbase + r;
       // unconditional load of a clamped row, zeroed below (no branch per load)
       const int tc = min(max(t, 0), T - 1);
-#ifdef JANUS_ABL_NOSTAGE  // timing ablation only (wrong results)
-      pf[i] = make_uint4(tc, 0, 0, 0);
-#else
       pf[i] = ld_act(xb + (int64_t)tc * C + cc * 8);
-#endif
       if (!(r < R0 && t >= 0 && t < T)) pf[i] = make_uint4(0, 0, 0, 0);
     }
 #pragma unroll
@@ -358,12 +326,7 @@ __global__ __launch_bounds__((WideGeo<C, V>::NT), (WideGeo<C, V>::MINB)) void re
       const int r = idx / CPR, cc = idx % CPR;
       if (r < R0) {
         half8 v = *reinterpret_cast<const half8*>(&pf[i]);
-#ifdef JANUS_ABL_NOSILU
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (_Float16)WSILU((float)v[j]);
-#else
         v = silu_h8(v);
-#endif
         *reinterpret_cast<half8*>(sX + r * LI + cc * 8) = v;
       }
     }
@@ -396,15 +359,16 @@ __global__ __launch_bounds__((WideGeo<C, V>::NT), (WideGeo<C, V>::MINB)) void re
           const int r = m * 16 + 4 * (lane >> 4) + rr;
           const int t = t0 - p2 + r;
           // c2 zero-pads its input outside [0, T): a 0/1 factor, not a branch per element
-          v[rr] = WSILU(acc[j][n][rr] + bias) * ((r < R1 && t >= 0 && t < T) ? 1.0f : 0.0f);
+          v[rr] = silu(acc[j][n][rr] + bias) * ((r < R1 && t >= 0 && t < T) ? 1.0f : 0.0f);
         }
-        st_frag_f16_pairs(sS, LI, m * 16 + 4 * (lane >> 4), co, v, lane);
+        st_frag_f16(sS, LI, m * 16 + 4 * (lane >> 4), co, v);
       }
     }
   }
   __syncthreads();
 
-  // residual x and accumulator rows of this tile (before c2 when Cfg::EPF)
+  // residual x and accumulator rows of this tile (loaded after c2: the registers do not
+  // allow them in flight during it)
   uint4 rq[G::NE], pq[G::NE];
   auto epi_load = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -413,24 +377,18 @@ __global__ __launch_bounds__((WideGeo<C, V>::NT), (WideGeo<C, V>::MINB)) void re
       const int r = idx / CPR, cg = (idx % CPR) * 8;
       const bool ok = r < BM && t0 + r < T;
       const int64_t o = (int64_t)(t0 + r) * C + cg;
-#ifdef JANUS_ABL_NORES  // timing ablation only (wrong results)
-      rq[i] = make_uint4(o, 0, 0, 0);
-      pq[i] = make_uint4(ok, 0, 0, 0);
-#else
       if constexpr (RES) rq[i] = rx[i];
       else rq[i] = ok ? ld_res(xb + o) : make_uint4(0, 0, 0, 0);
       pq[i] = (ok && a.accumulate) ? ld_res(ob + o) : make_uint4(0, 0, 0, 0);
-#endif
     }
   };
   JANUS_PROF(4);
-  if constexpr (G::Cfg::EPF) epi_load();
 
   // ---- 3. c2 over BM rows (row r <-> time t0 + r): A = sS[r + tap]
   f32x4 acc2[MW2][NTW];
   wide_conv<C, MW2, MT2, G, AROT>(acc2, a.w2, sS, 1, nks, wm, a_lane, b_lane);
   JANUS_PROF(5);
-  if constexpr (!G::Cfg::EPF) epi_load();
+  epi_load();
   __syncthreads();  // sS dead: the fp32 epilogue tile takes its place
   JANUS_PROF(6);
 
@@ -509,11 +467,11 @@ extern "C" int janus_debug_phase_read(long long* dst, int cap) {
 namespace janus {
 #endif
 
-template <int C, int V, int KC, int DC>
+template <int C, int KC, int DC>
 static void wide_go(const ResUnitArgs& a, hipStream_t s) {
-  using G = WideGeo<C, V>;
+  using G = WideGeo<C>;
   static_assert(G::LDS <= 160 * 1024, "LDS");
-  auto kern = resunit_wide_kernel<C, V, KC, DC>;
+  auto kern = resunit_wide_kernel<C, KC, DC>;
   static bool attr = false;
   if (!attr) {
     JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -529,50 +487,37 @@ static void wide_go(const ResUnitArgs& a, hipStream_t s) {
   JANUS_LAUNCH_CHECK();
 }
 
-template <int C, int V>
+template <int C>
 static void wide_cfg(const ResUnitArgs& a, hipStream_t s) {
-  using G = WideGeo<C, V>;
+  using G = WideGeo<C>;
   JANUS_CHECK((a.k - 1) * a.d <= 50 && a.k <= 11, "resunit (wide): (k-1)*d must be <= 50, k <= 11");
   JANUS_CHECK((a.k * C / 32) % G::NPB == 0, "resunit (wide): k-step count vs ring depth");
   // Firefly-GAN's ResBlock1 geometry (k in {3, 7, 11} x d in {1, 3, 5}) at compile time with
-  // the residual kept resident; JANUS_WIDE_RES=0 (A/B) or any other (k, d): run-time form
-  static const bool res = [] { const char* e = ab_env("JANUS_WIDE_RES"); return e ? std::atoi(e) != 0 : true; }();
-  constexpr bool fits = G::NT % G::CPR == 0 && (G::BM * G::CPR) % G::NT == 0 &&
-                        G::BM * G::CPR / G::NT == G::NE;
-  if constexpr (fits) {
-    if (res) {
+  // the residual kept resident; any other (k, d): run-time form
 #define JANUS_WIDE_KD(K_, D_) \
-    if (a.k == K_ && a.d == D_) return wide_go<C, V, K_, D_>(a, s);
-    JANUS_WIDE_KD(3, 1) JANUS_WIDE_KD(3, 3) JANUS_WIDE_KD(3, 5)
-    JANUS_WIDE_KD(7, 1) JANUS_WIDE_KD(7, 3) JANUS_WIDE_KD(7, 5)
-    JANUS_WIDE_KD(11, 1) JANUS_WIDE_KD(11, 3) JANUS_WIDE_KD(11, 5)
+  if (a.k == K_ && a.d == D_) return wide_go<C, K_, D_>(a, s);
+  JANUS_WIDE_KD(3, 1) JANUS_WIDE_KD(3, 3) JANUS_WIDE_KD(3, 5)
+  JANUS_WIDE_KD(7, 1) JANUS_WIDE_KD(7, 3) JANUS_WIDE_KD(7, 5)
+  JANUS_WIDE_KD(11, 1) JANUS_WIDE_KD(11, 3) JANUS_WIDE_KD(11, 5)
 #undef JANUS_WIDE_KD
-    }
-  }
-  wide_go<C, V, 0, 0>(a, s);
+  wide_go<C, 0, 0>(a, s);
 }
 
-template <int C, int V = 0> struct LdsCfg;
+template <int C> struct LdsCfg;
 // ---------------------------------------------------------------------------------
 // Variant with the weights staged through LDS (one copy per block, double-buffered,
 // each k-block's loads issued two k-blocks ahead into registers): measured faster where
-// all waves share the weight columns (C = 64: 4 waves x 64 columns) or where the per-wave
-// column slice is wide (C = 256), i.e. where direct per-wave B loads would exceed the
-// L2 -> CU rate. Same packed layout ([k-step][Cout][32]).
-// BM output rows per block, WM x WN waves, KB = K per weight k-block.
+// all waves share the weight columns (C = 64: 4 waves x 64 columns), i.e. where direct
+// per-wave B loads would exceed the L2 -> CU rate (the register ring at C = 64: 30.9-31.1
+// vs 30.2 ms, standalone 64 x 30 s). Same packed layout ([k-step][Cout][32]).
+// BM output rows per block, WM x WN waves, KB = K per weight k-block. Twice the waves per
+// block (4 x 2) measured slower (64 x 30 s, whole GPU: C = 64 30.4 -> 34.5 ms): the narrow
+// units' gain from more waves (resunit.hip) does not carry over to these MFMA-heavier tiles.
 template <> struct LdsCfg<64> { static constexpr int BM = 176, WM = 4, WN = 1, KB = 32; };
-template <> struct LdsCfg<256> { static constexpr int BM = 112, WM = 2, WN = 4, KB = 32; };
-// twice the waves per block (JANUS_WIDE64_WAVES=8 / JANUS_WIDE256_WAVES=16): fewer m-tiles
-// or n-tiles per wave, fewer registers, more waves per SIMD to hide the block's phases.
-// Measured (64 x 30 s, whole GPU): C = 64 30.4 -> 34.5 ms, C = 256 level (28.4); the
-// narrow units' gain from more waves (resunit.hip) does not carry over to these
-// MFMA-heavier tiles. A/B switches only.
-template <> struct LdsCfg<64, 1> { static constexpr int BM = 176, WM = 4, WN = 2, KB = 32; };
-template <> struct LdsCfg<256, 1> { static constexpr int BM = 112, WM = 4, WN = 4, KB = 32; };
 
-template <int C, int V = 0>
+template <int C>
 struct LdsGeo {
-  using Cfg = LdsCfg<C, V>;
+  using Cfg = LdsCfg<C>;
   static constexpr int BM = Cfg::BM, WM = Cfg::WM, WN = Cfg::WN, KB = Cfg::KB;
   static constexpr int NW = WM * WN, NT = NW * 64;
   static constexpr int LI = frag_pitch(C);        // activation row pitch (halves)
@@ -602,14 +547,14 @@ struct LdsGeo {
   static_assert((C / KB) % 2 == 0, "even k-block count (two register slots)");
 };
 
-// EPF: load the residual / accumulator rows at c2's start (in flight during its MFMAs)
-// instead of after its last k-block (costs 2*NE*4 VGPRs across the c2 loop).
+// The residual / accumulator rows are loaded at c2's start (in flight during its MFMAs;
+// costs 2*NE*4 VGPRs across the c2 loop).
 // KC / DC: the unit's (k, d) at compile time (0: run-time a.k / a.d) — Firefly's nine
 // ResBlock1 geometries get constant tap offsets, k-block counts and staged-row counts
-template <int C, bool EPF, int V, int KC = 0, int DC = 0>
-__global__ __launch_bounds__((LdsGeo<C, V>::NT), 3) void resunit_wide_lds_kernel(ResUnitArgs a,
+template <int C, int KC = 0, int DC = 0>
+__global__ __launch_bounds__((LdsGeo<C>::NT), 3) void resunit_wide_lds_kernel(ResUnitArgs a,
                                                                          int tiles_per_utt) {
-  using G = LdsGeo<C, V>;
+  using G = LdsGeo<C>;
   constexpr int BM = G::BM, WM = G::WM, KB = G::KB, NT = G::NT, LI = G::LI, LW = G::LW;
   constexpr int CPR = G::CPR, MT1 = G::MT1, MT2 = G::MT2, MW1 = G::MW1, MW2 = G::MW2;
   constexpr int NTW = G::NTW, ES = G::ES;
@@ -625,7 +570,7 @@ __global__ __launch_bounds__((LdsGeo<C, V>::NT), 3) void resunit_wide_lds_kernel
   const int R0 = MT1 * 16 + (k - 1) * d;       // x rows c1 reads
   // consecutive tiles on one XCD: a tile's halo rows are its neighbour's, staged through
   // the same L2
-  const int tile = tile_remap(blockIdx.x, gridDim.x);
+  const int tile = xcd_remap(blockIdx.x, gridDim.x);
   const int b = tile / tiles_per_utt, t0 = (tile % tiles_per_utt) * BM;
   const int tid = threadIdx.x, lane = tid & 63, wid = wave_id();
   const int wm = wid % WM, wn = wid / WM;
@@ -660,20 +605,17 @@ __global__ __launch_bounds__((LdsGeo<C, V>::NT), 3) void resunit_wide_lds_kernel
   // ---- 1. stage silu(x): all loads in flight, then convert + store
   {
     const int xbase = t0 - p2 - p1;
-    // window rows [0, R0 - BM) are the previous tile's, [BM, R0) the next tile's: those
-    // stay in L2 for the neighbour (per wave: any of its rows shared)
-    const int wr0 = wid * 64 / CPR;  // first window row of this wave at i = 0
+    // every staged row stays in L2: the halo rows for the neighbouring tile, the body rows
+    // for this tile's residual re-read (mfma.h ld_act_halo)
     uint4 pf[G::NLD];
 #pragma unroll
     for (int i = 0; i < G::NLD; ++i) {
       const int idx = tid + i * NT;
       const int r = idx / CPR, cc = idx % CPR;
       const int t = xbase + r;
-      const int rw = wr0 + i * (NT / CPR);  // wave-uniform
-      const bool keep = JANUS_STAGE_KEEP_ALL || rw < R0 - BM || rw + 64 / CPR > BM;
       // unconditional load of a clamped row, zeroed below (no branch per load)
       const int tc = min(max(t, 0), T - 1);
-      pf[i] = ld_act_halo(xb + (int64_t)tc * C + cc * 8, keep);
+      pf[i] = ld_act_halo(xb + (int64_t)tc * C + cc * 8, true);
       if (!(r < R0 && t >= 0 && t < T)) pf[i] = make_uint4(0, 0, 0, 0);
     }
     WIDE_WLOAD(rwA0, rwA1, a.w1, 0);
@@ -684,12 +626,7 @@ __global__ __launch_bounds__((LdsGeo<C, V>::NT), 3) void resunit_wide_lds_kernel
       const int r = idx / CPR, cc = idx % CPR;
       if (r < R0) {
         half8 v = *reinterpret_cast<const half8*>(&pf[i]);
-#ifdef JANUS_ABL_NOSILU
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (_Float16)WSILU((float)v[j]);
-#else
         v = silu_h8(v);
-#endif
         *reinterpret_cast<half8*>(sX + r * LI + cc * 8) = v;
       }
     }
@@ -775,9 +712,9 @@ __global__ __launch_bounds__((LdsGeo<C, V>::NT), 3) void resunit_wide_lds_kernel
           const int r = m * 16 + 4 * (lane >> 4) + rr;
           const int t = t0 - p2 + r;
           // c2 zero-pads its input outside [0, T): a 0/1 factor, not a branch per element
-          v[rr] = WSILU(acc[j][n][rr] + bias) * ((r < R1 && t >= 0 && t < T) ? 1.0f : 0.0f);
+          v[rr] = silu(acc[j][n][rr] + bias) * ((r < R1 && t >= 0 && t < T) ? 1.0f : 0.0f);
         }
-        st_frag_f16_pairs(sS, LI, m * 16 + 4 * (lane >> 4), co, v, lane);
+        st_frag_f16(sS, LI, m * 16 + 4 * (lane >> 4), co, v);
       }
     }
     WIDE_WSTORE(rwA0, rwA1, 0);
@@ -797,7 +734,7 @@ __global__ __launch_bounds__((LdsGeo<C, V>::NT), 3) void resunit_wide_lds_kernel
       pq[i] = (ok && a.accumulate) ? ld_res(ob + o) : make_uint4(0, 0, 0, 0);
     }
   };
-  if constexpr (EPF) epi_load();
+  epi_load();
 
   // ---- 3. c2 over BM rows (row r <-> time t0 + r): A = sS[r + tap]
   f32x4 acc2[MW2][NTW];
@@ -806,7 +743,6 @@ __global__ __launch_bounds__((LdsGeo<C, V>::NT), 3) void resunit_wide_lds_kernel
 #pragma unroll
     for (int n = 0; n < NTW; ++n) acc2[j][n] = zero_f32x4();
   WIDE_KLOOP(acc2, MW2T, MT2T, a.w2, sS, 1);
-  if constexpr (!EPF) epi_load();
 
   // ---- 4. epilogue: c2 + b2 -> fp32 LDS tile (sS dead), then 16-byte row chunks
 #pragma unroll
@@ -847,11 +783,11 @@ __global__ __launch_bounds__((LdsGeo<C, V>::NT), 3) void resunit_wide_lds_kernel
 #undef WIDE_WSTORE
 #undef WIDE_KLOOP
 
-template <int C, bool EPF, int V, int KC, int DC>
+template <int C, int KC, int DC>
 static void lds_go(const ResUnitArgs& a, hipStream_t s) {
-  using G = LdsGeo<C, V>;
+  using G = LdsGeo<C>;
   static_assert(G::LDS <= 160 * 1024, "LDS");
-  auto kern = resunit_wide_lds_kernel<C, EPF, V, KC, DC>;
+  auto kern = resunit_wide_lds_kernel<C, KC, DC>;
   static bool attr = false;
   if (!attr) {
     JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -863,30 +799,24 @@ static void lds_go(const ResUnitArgs& a, hipStream_t s) {
   JANUS_LAUNCH_CHECK();
 }
 
-template <int C, bool EPF, int V>
+template <int C>
 static void lds_cfg(const ResUnitArgs& a, hipStream_t s) {
   JANUS_CHECK((a.k - 1) * a.d <= 50 && a.k <= 11, "resunit (wide): (k-1)*d must be <= 50, k <= 11");
   // Firefly-GAN's ResBlock1 geometry (k in {3, 7, 11} x d in {1, 3, 5}) compiled per (k, d)
-  // for C = 64 (r05; JANUS_WIDE_LDS_RT=1: the run-time form, A/B): standalone 64 x 30 s
-  // forward, C = 64 units 29.7-29.8 vs 30.7 ms; step 250.3-251.2 vs 251.5-251.9 ms
-  // (profiles/r05_c64_kd_ab.txt); any other (k, d) and C run the run-time form
-  static const bool rt = ab_env("JANUS_WIDE_LDS_RT") != nullptr;
-  if constexpr (C == 64 && V == 0) {
-    if (!rt) {
+  // (r05): against the run-time form, standalone 64 x 30 s forward, C = 64 units 29.7-29.8
+  // vs 30.7 ms; step 250.3-251.2 vs 251.5-251.9 ms (profiles/r05_c64_kd_ab.txt); any other
+  // (k, d) runs the run-time form
 #define JANUS_LDS_KD(K_, D_) \
-      if (a.k == K_ && a.d == D_) return lds_go<C, EPF, V, K_, D_>(a, s);
-      JANUS_LDS_KD(3, 1) JANUS_LDS_KD(3, 3) JANUS_LDS_KD(3, 5)
-      JANUS_LDS_KD(7, 1) JANUS_LDS_KD(7, 3) JANUS_LDS_KD(7, 5)
-      JANUS_LDS_KD(11, 1) JANUS_LDS_KD(11, 3) JANUS_LDS_KD(11, 5)
+  if (a.k == K_ && a.d == D_) return lds_go<C, K_, D_>(a, s);
+  JANUS_LDS_KD(3, 1) JANUS_LDS_KD(3, 3) JANUS_LDS_KD(3, 5)
+  JANUS_LDS_KD(7, 1) JANUS_LDS_KD(7, 3) JANUS_LDS_KD(7, 5)
+  JANUS_LDS_KD(11, 1) JANUS_LDS_KD(11, 3) JANUS_LDS_KD(11, 5)
 #undef JANUS_LDS_KD
-    }
-  }
-  lds_go<C, EPF, V, 0, 0>(a, s);
+  lds_go<C, 0, 0>(a, s);
 }
 
 bool resunit_wide_supported(int C, int k, int d) {
-  static const bool off = ab_env("JANUS_NO_WIDE_UNITS") != nullptr;
-  return !off && (C == 64 || C == 128 || C == 256) && k >= 1 && k <= 11 && (k & 1) &&
+  return (C == 64 || C == 128 || C == 256) && k >= 1 && k <= 11 && (k & 1) &&
          (k - 1) * d <= 50;
 }
 
@@ -897,35 +827,9 @@ void resunit_wide_pack(const float* w, _Float16* out, int C, int k, hipStream_t 
 }
 
 void resunit_wide_launch(const ResUnitArgs& a, hipStream_t s) {
-  static const int epf = [] { const char* e = ab_env("JANUS_WIDE_EPF"); return e ? std::atoi(e) : 1; }();
-  static const int w64 = ab_env("JANUS_WIDE64_WAVES") ? std::atoi(ab_env("JANUS_WIDE64_WAVES")) : 4;
-  static const int w256 = ab_env("JANUS_WIDE256_WAVES") ? std::atoi(ab_env("JANUS_WIDE256_WAVES")) : 8;
-  if (a.C == 64) {
-    static const std::string c64 = ab_env("JANUS_WIDE64_CFG") ? ab_env("JANUS_WIDE64_CFG") : "lds";
-    if (c64 == "ring") wide_cfg<64, 5>(a, s);
-    else if (w64 == 8) epf ? lds_cfg<64, true, 1>(a, s) : lds_cfg<64, false, 1>(a, s);
-    else epf ? lds_cfg<64, true, 0>(a, s) : lds_cfg<64, false, 0>(a, s);
-  }
-  else if (a.C == 128) {
-    // JANUS_WIDE128_CFG: 2 (default) = 4 waves, weight ring 2 deep (166 VGPRs, three blocks
-    // per CU); 0 = ring 4 deep (178 VGPRs, two blocks); 1 = 8 waves. Standalone 64 x 30 s,
-    // C = 128 units: 45.4 / 49.0 / 59.6 ms (46.5 before the issue order was pinned)
-    static const int c128 = ab_env("JANUS_WIDE128_CFG") ? std::atoi(ab_env("JANUS_WIDE128_CFG")) : 2;
-    if (c128 == 1) wide_cfg<128, 1>(a, s);
-    else if (c128 == 0) wide_cfg<128, 0>(a, s);
-    else wide_cfg<128, 2>(a, s);
-  }
-  else if (a.C == 256) {
-    // JANUS_WIDE256_CFG: ring4 (default: weights from L2 into a per-wave register ring 4
-    // deep, 8 waves x 32 columns; standalone 64 x 30 s, C = 256 units 27.0 -> 22.3 ms;
-    // overlapped step, vocoder side 289 -> 282 ms), ring (2 deep: 22.8 ms), lds (weights
-    // staged through LDS, the r01 form)
-    static const std::string c256 = ab_env("JANUS_WIDE256_CFG") ? ab_env("JANUS_WIDE256_CFG") : "ring4";
-    if (c256 == "ring") wide_cfg<256, 3>(a, s);
-    else if (c256 == "ring4") wide_cfg<256, 4>(a, s);
-    else if (w256 == 16) epf ? lds_cfg<256, true, 1>(a, s) : lds_cfg<256, false, 1>(a, s);
-    else epf ? lds_cfg<256, true, 0>(a, s) : lds_cfg<256, false, 0>(a, s);
-  }
+  if (a.C == 64) lds_cfg<64>(a, s);
+  else if (a.C == 128) wide_cfg<128>(a, s);
+  else if (a.C == 256) wide_cfg<256>(a, s);
   else throw Error("resunit (wide): C must be 64, 128 or 256");
 }
 

@@ -54,7 +54,6 @@ struct janus_vocoder {
   std::vector<janus::VConv> ups;
   std::vector<janus::VConv> rb;  // [stage][kernel][dilation][conv1|conv2]
   std::vector<janus::VUnit> units;  // same indexing / 2, fused path (C <= 32)
-  bool fuse = true;
   const float* post_w = nullptr;
   float post_b = 0.f;
   janus::DevMem buf[5];
@@ -225,7 +224,7 @@ static void forward(janus_vocoder* v, const _Float16* lat, int B, int F, float* 
       const _Float16* x = U;
       for (int m = 0; m < c.n_dilations; ++m) {
         const VUnit& U = v->units[rb_index(c, i, kj, m, 0) / 2];
-        if (v->fuse && U.c > 0) {
+        if (U.c > 0) {
           if (m + 1 < c.n_dilations) {
             _Float16* xn = X[m & 1];
             run_unit(v, U, x, xn, B, T, 1.0f, 0, s);
@@ -284,7 +283,6 @@ extern "C" int janus_vocoder_create(const janus_vocoder_config* cfg, janus_vocod
                 "vocoder: bad config");
     auto* v = new janus_vocoder();
     v->cfg = *cfg;
-    v->fuse = ab_env("JANUS_NO_FUSE") == nullptr;
     *out = v;
   });
 }

@@ -25,7 +25,6 @@
 // then per-split partial (C, m, l) in fp32; xattn_combine merges the splits into
 // c[b][h*D + j] fp16, the A operand of the per-head Wv GEMM.
 #include "mfma.h"
-#include <cstdlib>
 #include "kernels.h"
 #include "xattn_body.h"
 
@@ -66,12 +65,12 @@ void xattn_absorb(const float* wq, const float* bq, const float* wk, int D, int 
 }
 
 template <int D, int CH, bool PAIR = false, bool DIRECT = false, bool PF2 = false, bool ROWLD = false>
-__global__ __launch_bounds__(CH * 8, (PF2 && !ROWLD) ? 1 : (CH == 32 ? (D > 512 ? 2 : 3) : 2)) void xattn_kernel(
+__global__ __launch_bounds__(CH * 8, PF2 ? 1 : 2) void xattn_kernel(
     const _Float16* __restrict__ qk, const _Float16* __restrict__ enc, int Te, int H, int kps,
     float* __restrict__ part_c, float* __restrict__ part_ml, const int4* __restrict__ pairs,
     _Float16* __restrict__ out = nullptr, int rev = 0) {
   extern __shared__ __attribute__((aligned(16))) _Float16 smem[];
-  JANUS_DEC_WAVE_PRIO();
+  dec_wave_prio();
   xattn_body<D, CH, PAIR, DIRECT, PF2, false, ROWLD>(qk, enc, Te, H, kps, part_c, part_ml, pairs, out,
                                                      blockIdx.x, gridDim.x, blockIdx.y, smem, rev != 0);
 }
@@ -255,11 +254,7 @@ __global__ __launch_bounds__(CH * 8, 1) void xattn_group_kernel(
       float* pc = part_c + (((int64_t)row_b(row) * nsplit + s) * H + (row & 7)) * D;
 #pragma unroll
       for (int n = 0; n < NT; ++n)
-#ifndef JANUS_XPART_PLAIN
         __builtin_nontemporal_store(accc[mt][n][r], &pc[w * (D / NW) + 16 * n + lr]);
-#else
-        pc[w * (D / NW) + 16 * n + lr] = accc[mt][n][r];
-#endif
     }
   if (lane == 0) {
 #pragma unroll
@@ -505,11 +500,7 @@ __global__ __launch_bounds__(CH * 8, NMT == 1 ? 2 : 1) void xattn_rows_kernel(
       float* pc = part_c + (((int64_t)row_b(row) * nsplit + s) * H + row_h(row)) * D;
 #pragma unroll
       for (int n = 0; n < NT; ++n)
-#ifndef JANUS_XPART_PLAIN
         __builtin_nontemporal_store(accc[mt][n][r], &pc[w * (D / NW) + 16 * n + lr]);
-#else
-        pc[w * (D / NW) + 16 * n + lr] = accc[mt][n][r];
-#endif
     }
   if (lane == 0) {
 #pragma unroll
@@ -689,15 +680,9 @@ __global__ __launch_bounds__(1024) void xattn_combine_vproj_kernel(
       for (int s = 0; s < kXCombMax; ++s) {
         if (s < nsplit) {
           ml[s] = *reinterpret_cast<const float2*>(pml + ((int64_t)s * H + h) * 2);
-#ifndef JANUS_XPART_PLAIN
-        {
           typedef float f2v __attribute__((ext_vector_type(2)));
           const f2v t = __builtin_nontemporal_load(reinterpret_cast<const f2v*>(pc + (int64_t)s * HD));
           v[s] = make_float2(t.x, t.y);
-        }
-#else
-          v[s] = *reinterpret_cast<const float2*>(pc + (int64_t)s * HD);
-#endif
         }
       }
       float M = -INFINITY;
@@ -773,24 +758,6 @@ int xattn_split_count(int Te, int requested) {
   return std::max(n, 1);
 }
 
-#ifndef JANUS_XATTN_FRAG
-constexpr bool kXattnRow = true;   // one-split D = 512: whole-row loads (ROWLD)
-#else
-constexpr bool kXattnRow = false;  // A/B build: the fragment-pattern loads
-#endif
-// one-split row loads with two chunks in flight per wave (two register sets of 8 rows):
-// 158 VGPRs, one block per CU — measured slower at 256 rows (decoder 1539 vs 1444 us per
-// position in the staggered step, profiles/r06_xattn_ab.txt); A/B build only
-#ifdef JANUS_XATTN_ROW2
-constexpr bool kXattnRowPF2 = true;
-#else
-constexpr bool kXattnRowPF2 = false;
-#endif
-#ifndef JANUS_XATTN_PF1
-constexpr bool kXattnPF2 = true;
-#else
-constexpr bool kXattnPF2 = false;  // A/B build: one chunk in flight
-#endif
 template <int D, int CH>
 static void xattn_cfg(const _Float16* qk, const _Float16* enc, int B, int Te, int H, int nsplit,
                       float* part_c, float* part_ml, hipStream_t s, const int4* pairs, int npairs,
@@ -798,12 +765,15 @@ static void xattn_cfg(const _Float16* qk, const _Float16* enc, int B, int Te, in
   const int chunks = (Te + CH - 1) / CH;
   const int kps = (chunks + nsplit - 1) / nsplit * CH;
   const bool direct = out != nullptr;
-  constexpr bool row = kXattnRow && D == 512 && CH == 64;
+  // one split: D = 512 loads whole rows (ROWLD) with one chunk in flight — two in flight
+  // (two register sets of 8 rows: 158 VGPRs, one block per CU) measured slower at 256 rows
+  // (decoder 1539 vs 1444 us per position in the staggered step,
+  // profiles/r06_xattn_ab.txt); the fragment-pattern loads keep two chunks in flight (PF2)
+  constexpr bool row = D == 512 && CH == 64;
   decltype(&xattn_kernel<D, CH, false>) kern;
   if (direct) {
-    if constexpr (row) kern = kXattnRowPF2 ? xattn_kernel<D, CH, false, true, true, true>
-                                           : xattn_kernel<D, CH, false, true, false, true>;
-    else kern = xattn_kernel<D, CH, false, true, kXattnPF2>;
+    if constexpr (row) kern = xattn_kernel<D, CH, false, true, false, true>;
+    else kern = xattn_kernel<D, CH, false, true, true>;
   } else {
     kern = pairs ? xattn_kernel<D, CH, true> : xattn_kernel<D, CH, false>;
   }
@@ -844,23 +814,16 @@ void xattn_launch(const _Float16* qk, const _Float16* enc, int B, int Te, int D,
   if (B <= 0 || Te <= 0) return;
   JANUS_CHECK(nsplit >= 1 && nsplit <= 63, "xattn: 1..63 key splits");
   JANUS_CHECK(!pairs || (H <= 8 && npairs >= 1 && D <= 512), "xattn: row pairs need H <= 8, D <= 512");
-  // 64-key chunks (8 waves) unless JANUS_XATTN_CH32
-  static const bool ch32 = ab_env("JANUS_XATTN_CH32") != nullptr;
   // one key split with the merge requested: the kernel writes c itself (DIRECT), no merge
-  if (combine && nsplit == 1 && !pairs && !ch32 && D <= 512) {
+  if (combine && nsplit == 1 && !pairs && D <= 512) {
     if (D == 384) xattn_cfg<384, 64>(qk, enc, B, Te, H, 1, part_c, part_ml, s, nullptr, 0, out);
     else xattn_cfg<512, 64>(qk, enc, B, Te, H, 1, part_c, part_ml, s, nullptr, 0, out, rev);
     return;
   }
-  if (D == 384) {
-    if (ch32) xattn_cfg<384, 32>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
-    else xattn_cfg<384, 64>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
-  } else if (D == 512) {
-    if (ch32) xattn_cfg<512, 32>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
-    else xattn_cfg<512, 64>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
-  } else {
-    xattn_cfg<768, 32>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
-  }
+  // 64-key chunks (8 waves); D = 768: 32-key chunks
+  if (D == 384) xattn_cfg<384, 64>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
+  else if (D == 512) xattn_cfg<512, 64>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
+  else xattn_cfg<768, 32>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
   if (!combine) return;  // the caller merges (xattn_combine_vproj_launch)
   if (nsplit <= kXCombMax && D <= 512)
     xattn_combine_wide_kernel<<<dim3(H, B), 128, 0, s>>>(part_c, part_ml, nsplit, H, D, out);

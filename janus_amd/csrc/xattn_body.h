@@ -127,14 +127,7 @@ __device__ __forceinline__ void xattn_body(
     const _Float16* src = eb + (int64_t)key * D + kh * KH + 8 * lg;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
-#ifdef JANUS_XATTN_NT
-    {
-      const uint4 u = ok ? ld_nt(src + 32 * ks) : make_uint4(0, 0, 0, 0);
-      dst[ks] = *reinterpret_cast<const half8*>(&u);
-    }
-#else
       dst[ks] = ok ? *reinterpret_cast<const half8*>(src + 32 * ks) : zero_half8();
-#endif
   };
 
   f32x4 accc[NT];
@@ -285,11 +278,8 @@ __device__ __forceinline__ void xattn_body(
     float* pc = part_c + (((int64_t)row_b(row) * nsplit + s) * H + row_h(row)) * D;
 #pragma unroll
     for (int n = 0; n < NT; ++n)
-#ifndef JANUS_XPART_PLAIN  // partials written / read past the caches (r03 v4; A/B switch)
+      // partials written / read past the caches (r03 v4)
       __builtin_nontemporal_store(accc[n][r], &pc[w * (D / NW) + 16 * n + lr]);
-#else
-      pc[w * (D / NW) + 16 * n + lr] = accc[n][r];
-#endif
   }
   if (lane == 0) {
 #pragma unroll

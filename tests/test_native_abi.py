@@ -112,7 +112,7 @@ def test_decode_path_flags_match_header():
 
 
 def test_product_library_reads_no_tuning_environment():
-    """Kernel-geometry A/B switches exist only in -DJANUS_AB_KNOBS builds (common.h ab_env):
-    the product library carries no JANUS_* environment name."""
+    """Each kernel is compiled in one form and takes no tuning from the environment: the
+    product library carries no JANUS_* environment name."""
     data = open(_native.LIB_PATH, "rb").read()
     assert not re.findall(rb"JANUS_[A-Z0-9_]+\x00", data)

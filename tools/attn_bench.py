@@ -28,8 +28,7 @@ def main():
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 20
     fl = 4.0 * B * H * T * T * 64
-    print(f"attention B={B} T={T} H={H}: {ms:.3f} ms {fl / ms / 1e9:.1f} TF/s "
-          f"({'v1' if os.environ.get('JANUS_ATTN_V1') else 'st'})", flush=True)
+    print(f"attention B={B} T={T} H={H}: {ms:.3f} ms {fl / ms / 1e9:.1f} TF/s", flush=True)
 
 
 if __name__ == "__main__":

@@ -83,7 +83,7 @@ def kernel_split(windows):
         shutil.rmtree(out, ignore_errors=True)
     groups = {"logits_top2k": ("logits_partial_kernel",), "beam_step": ("beam_step_kernel",),
               "beam_reorder": ("beam_reorder_kernel",),
-              "self_attention": ("decode_attention_kernel", "decode_split_kernel", "decode_combine",
+              "self_attention": ("decode_split_kernel", "decode_combine",
                                  "decode_head_kernel"),
               "cross_attention": ("xattn",)}
     ns = {k: 0.0 for k in groups}
