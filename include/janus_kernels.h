@@ -257,6 +257,31 @@ int janus_decode_plan_describe(const janus_whisper_config* cfg, const janus_deco
                                char* text, int text_cap, int64_t* key, int key_cap, int32_t* n_key);
 
 /*
+ * Test-only view of the decoder's residual stream: a teacher-forced run of the decode call's
+ * own machinery (plan, buffers, uploads, cross K/V, then every position's embedding and
+ * layers with the plan's path flags and persistent level), launched directly, without the
+ * final LayerNorm / vocabulary projection / selection. No sampling and no beam search: the
+ * entry takes neither argument.
+ *   rows      the forced tokens are the per-row prompts, every row the same length n (the
+ *             entry runs with max_length = n + 1 whatever opt says); enc_index, pos_offset and
+ *             steps as in janus_whisper_decode_greedy_ex, the continuation checks and the
+ *             recorded stand (janus_whisper_decode_stand) included, so a second call with the
+ *             same n continues rows. A continuing row's tokens are taken from its prompt too.
+ *   x_out     [device] f32 [x_positions][batch][d_model]: row b of step i is the residual row
+ *             (before the decoder's final LayerNorm) of position pos_offset[b] + i. The call
+ *             runs steps positions (n when steps is 0 or the rows are not staggered) and
+ *             fails when x_positions is smaller.
+ *   kc_out / vc_out  [device, nullable] fp16 [dec_layers][batch][n_text_ctx][d_model]: the
+ *             self-attention caches after the last position.
+ *   plan_text [plan_cap]: the plan that ran, as janus_decode_plan_describe writes it.
+ * Waits for the stream; a persistent segment's barrier timeout is an error, not data.
+ */
+int janus_whisper_decode_hidden(janus_whisper* w, const uint16_t* enc, int batch,
+                                const janus_decode_options* opt, const janus_decode_rows* rows,
+                                float* x_out, int x_positions, uint16_t* kc_out, uint16_t* vc_out,
+                                char* plan_text, int plan_cap, void* stream);
+
+/*
  * Word alignment kernels (janus_whisper_align), one test entry each. Device pointers.
  *
  * janus_align_dtw_f32: the DTW of janus.h's rule 4 on x f32 [N][F] as given (the alignment

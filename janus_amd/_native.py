@@ -140,6 +140,8 @@ SIGNATURES = {
     # test-only view of the decode planner (no engine, no device)
     "janus_decode_plan_describe": [_P, _P, _P, _I32, _I32, _I32, _I32, _F32, _P, _I32, _P, _I32, _I32,
                                    _P, _I32, _P, _I32, _P],
+    # test-only view of the decoder's residual stream (teacher-forced decode machinery)
+    "janus_whisper_decode_hidden": [_P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, _P],
 }
 RESTYPES = {"janus_conv1d_packed_size": ctypes.c_int64}
 

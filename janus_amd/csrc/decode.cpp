@@ -539,10 +539,17 @@ struct DecodeStep : LaneBuffers {
   // the embedding and every layer of position pos: the residual rows x before the final
   // LayerNorm (the decode call's tail, or the language head of detect_lane, comes after)
   void forward(int pos) const {
-    if (!(P.fuse_se && pos >= P.sample_begin && pos > 0))
-      embed_launch(w->tok16.as<_Float16>(), pos_emb, tokens, maxlen, pos, d, x,
-                   fused_ln ? lnp : nullptr, B, s, w->dec[0].ln1g, w->dec[0].ln1b,
-                   (ln_fuse || (embed_ln && !layerk)) ? a : nullptr, roff);
+    if (!(P.fuse_se && pos >= P.sample_begin && pos > 0)) embed(pos);
+    layers(pos);
+  }
+  // the rows' tokens at pos embedded into x (a decode call's sampled positions get theirs
+  // from the previous position's select_embed instead)
+  void embed(int pos) const {
+    embed_launch(w->tok16.as<_Float16>(), pos_emb, tokens, maxlen, pos, d, x,
+                 fused_ln ? lnp : nullptr, B, s, w->dec[0].ln1g, w->dec[0].ln1b,
+                 (ln_fuse || (embed_ln && !layerk)) ? a : nullptr, roff);
+  }
+  void layers(int pos) const {
     for (int l = 0; l < nl; ++l) {
       DecLayer& L = w->dec[l];
       qkv_self_attention(l, pos);
@@ -714,9 +721,87 @@ static void detect_lane(janus_whisper* w, DecLane& Z, const _Float16* enc, int B
                    lang_begin, n_lang, B, probs, best, s);
 }
 
+// The residual rows of forced tokens (janus_whisper_decode_hidden, test entry): a decode
+// call's plan, buffers, uploads and cross K/V, then every position's embedding and layers
+// launched directly and x copied out after each — no tail, so no token is selected and the
+// embedding of every position comes from the embedding kernel.
+static void hidden_lane(janus_whisper* w, DecLane& Z, const DecodeCall& call, int B, float* x_out,
+                        int x_positions, _Float16* kc_out, _Float16* vc_out, char* text, int text_cap,
+                        hipStream_t s) {
+  lane_check(Z);
+  const DecodePlan P = plan_decode(w->cfg, *call.opt, call.rows, nullptr, nullptr, B, stream_cu_count(s), false,
+                                   LaneStand{&Z.stand, Z.stand_maxlen}, SegDevice{dec_seg_grid, dec_seg_resident});
+  JANUS_CHECK(P.steps <= x_positions, "decode_hidden: x_out holds fewer positions than the call runs");
+  const std::string desc = P.describe();
+  JANUS_CHECK(text && (int64_t)desc.size() < text_cap, "decode_hidden: plan_text too small");
+  std::memcpy(text, desc.c_str(), desc.size() + 1);
+  Z.stand.clear();
+  const LaneBuffers b = ensure_buffers(w, Z, P, call.opt->n_suppress, s);
+  const BeamState bst{};
+  upload_inputs(w, Z, P, b, call, bst, s);
+  // the forced tokens of every row: a continuing row's positions of this call too
+  JANUS_HIP(hipMemcpyAsync(b.tokens, P.init.data(), sizeof(int32_t) * (size_t)B * P.maxlen,
+                           hipMemcpyHostToDevice, s));
+  project_cross_kv(w, P, b, s);
+  const DecodeStep step(w, P, b, bst, s);
+  const int64_t xrow = (int64_t)B * w->cfg.d_model;
+  for (int pos = 0; pos < P.steps; ++pos) {
+    step.embed(pos);
+    step.layers(pos);
+    JANUS_HIP(hipMemcpyAsync(x_out + pos * xrow, b.x, sizeof(float) * xrow, hipMemcpyDeviceToDevice, s));
+  }
+  const int64_t cache = (int64_t)w->cfg.dec_layers * B * w->cfg.n_text_ctx * w->cfg.d_model;
+  if (kc_out) JANUS_HIP(hipMemcpyAsync(kc_out, b.kcache, sizeof(_Float16) * cache, hipMemcpyDeviceToDevice, s));
+  if (vc_out) JANUS_HIP(hipMemcpyAsync(vc_out, b.vcache, sizeof(_Float16) * cache, hipMemcpyDeviceToDevice, s));
+  uint32_t herr = 0;   // a segment that gave up at a barrier: an error, not data (as finish)
+  if (P.persist > 0)
+    JANUS_HIP(hipMemcpyAsync(&herr, Z.d_segerr.p, sizeof(herr), hipMemcpyDeviceToHost, s));
+  JANUS_HIP(hipStreamSynchronize(s));   // (P.init and herr die with this call)
+  if (herr) {
+    JANUS_HIP(hipMemsetAsync(Z.d_segbar.p, 0, sizeof(unsigned) * 256, s));
+    JANUS_HIP(hipMemsetAsync(Z.d_segerr.p, 0, 256, s));
+    JANUS_HIP(hipStreamSynchronize(s));
+    throw Error("decode: a persistent decoder segment timed out at a grid barrier (grid not co-resident)");
+  }
+  Z.last_positions = P.steps;
+  Z.last_launches = 0;
+  Z.last_enc_rows = P.enc_rows;
+  Z.last_persist = P.persist;
+  Z.stand.assign(B, 0);
+  for (int r = 0; r < B; ++r) Z.stand[r] = (P.stagger() ? P.roff[r] : 0) + P.steps;
+  Z.stand_maxlen = P.maxlen;
+}
+
 }  // namespace janus
 
 using namespace janus;
+
+extern "C" int janus_whisper_decode_hidden(janus_whisper* w, const uint16_t* enc, int batch,
+                                           const janus_decode_options* opt, const janus_decode_rows* rows,
+                                           float* x_out, int x_positions, uint16_t* kc_out, uint16_t* vc_out,
+                                           char* plan_text, int plan_cap, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(w && enc && opt && rows && x_out && plan_text, "null argument");
+    JANUS_CHECK(batch >= 1, "decode_hidden: batch must be >= 1");
+    JANUS_CHECK(rows->prompts && rows->prompt_lens, "decode_hidden: the forced tokens are the per-row prompts");
+    const int n = rows->prompt_lens[0];
+    for (int b = 0; b < batch; ++b)
+      JANUS_CHECK(rows->prompt_lens[b] == n, "decode_hidden: every row's prompt must have the same length");
+    JANUS_CHECK(opt->state_slot >= 0 && opt->state_slot < 8, "decode: state_slot must be 0 .. 7");
+    std::lock_guard<std::mutex> lk(w->mu);
+    hipStream_t s = (hipStream_t)stream;
+    prepare(w, s);
+    janus_decode_options o = *opt;
+    o.max_length = n + 1;   // every position is inside the prompt: nothing is sampled
+    while ((int)w->lanes.size() <= o.state_slot) w->lanes.emplace_back(new DecLane());
+    w->last_slot = o.state_slot;
+    hidden_lane(w, *w->lanes[o.state_slot],
+                DecodeCall{reinterpret_cast<const _Float16*>(enc), &o, rows, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr},
+                batch, x_out, x_positions, reinterpret_cast<_Float16*>(kc_out), reinterpret_cast<_Float16*>(vc_out),
+                plan_text, plan_cap, s);
+  });
+}
 
 extern "C" int janus_whisper_detect_language(janus_whisper* w, const uint16_t* enc, int batch, int sot_token,
                                              int lang_begin, int n_lang, float* probs, int32_t* best,

@@ -637,6 +637,69 @@ class WhisperEngine:
                                  f"tokens before its end (no_speech_back)")
         return back
 
+    def decode_hidden(self, enc: torch.Tensor, tokens, enc_index=None, pos_offset=None,
+                      steps: int = 0, want_cache: bool = True, xattn_splits: int = 0,
+                      cu_count: int = 0, state_slot: int = 0, msplit_rows_n: int = 0,
+                      persistent: int = 0, path_flags: int = 0):
+        """janus_whisper_decode_hidden (test entry): the decoder's residual rows of the forced
+        ``tokens`` int [B][n], through the decode call's own plan and launches (no final
+        LayerNorm, no selection). ``enc_index`` / ``pos_offset`` / ``steps`` / the options as
+        decode_ex. Returns a HiddenOut: ``x`` f32 [positions][B][d] (row b of step i is
+        position pos_offset[b] + i), the self-attention caches ``kc`` / ``vc`` fp16
+        [layers][B][n_text_ctx][d] (``want_cache``) and ``plan``, the plan that ran as a dict
+        of its name=value lines (ints; pairs / groups as lists)."""
+        tk = np.ascontiguousarray(np.asarray(tokens, np.int32))
+        if tk.ndim != 2 or tk.shape[1] < 1:
+            raise ValueError("tokens must be [B][n], n >= 1")
+        B, n = tk.shape
+        if B != (enc.shape[0] if enc_index is None else len(enc_index)):
+            raise ValueError("one token row per decoder row")
+        if steps and pos_offset is None:
+            raise ValueError("steps applies to a staggered call (pos_offset) only")
+        assert enc.dtype == torch.float16 and enc.is_contiguous()
+        c = self.cfg
+        opt = janus_decode_options()
+        opt.max_length = n + 1
+        opt.eot = opt.blank_token = opt.timestamp_begin = opt.no_timestamps = -1
+        opt.max_initial_timestamp_index = -1
+        opt.xattn_splits, opt.cu_count, opt.state_slot = xattn_splits, cu_count, state_slot
+        opt.msplit_rows_n, opt.persistent, opt.path_flags = msplit_rows_n, persistent, path_flags
+        rows = janus_decode_rows()
+        rows.no_speech_token = -1
+        plens = np.full(B, n, np.int32)
+        rows.prompts = tk.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        rows.prompt_lens = plens.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        rows.stride = n
+        po = ei = None
+        if pos_offset is not None:
+            po = np.ascontiguousarray(np.asarray(pos_offset, np.int32))
+            if po.shape != (B,):
+                raise ValueError("pos_offset needs one offset per row")
+            rows.pos_offset = po.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            rows.steps = int(steps)
+        if enc_index is not None:
+            ei = np.ascontiguousarray(np.asarray(enc_index, np.int32))
+            if ei.min() < 0 or ei.max() >= enc.shape[0]:
+                raise ValueError("enc_index out of range")
+            rows.enc_index = ei.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            rows.n_enc = int(enc.shape[0])
+        T = int(steps) if (pos_offset is not None and steps > 0) else n
+        x = torch.empty(T, B, c.d_model, dtype=torch.float32, device=self.device)
+        kc = vc = None
+        if want_cache:
+            kc = torch.empty(c.dec_layers, B, c.n_text_ctx, c.d_model, dtype=torch.float16, device=self.device)
+            vc = torch.empty_like(kc)
+        text = ctypes.create_string_buffer(1 << 16)
+        nat.call("janus_whisper_decode_hidden", self._h, enc.data_ptr(), B, ctypes.addressof(opt),
+                 ctypes.addressof(rows), x.data_ptr(), T, kc.data_ptr() if want_cache else None,
+                 vc.data_ptr() if want_cache else None, text, len(text), nat.stream_ptr())
+        del po, ei, plens
+        plan = {}
+        for line in text.value.decode().splitlines():
+            k, v = line.split("=", 1)
+            plan[k] = [int(t) for t in v.split(",") if t] if k in ("pairs", "groups") else int(float(v))
+        return HiddenOut(x, kc, vc, plan)
+
     def detect_language(self, enc: torch.Tensor):
         """janus_whisper_detect_language over ``enc`` [B][1500][d]: (probs f32 [B][n_languages]
         — the softmax over the language tokens alone of one <|startoftranscript|> position —,
@@ -774,6 +837,15 @@ def shared_rows_in_place(cfg) -> bool:
     if cfg is None:
         return True
     return cfg.n_heads <= 8 and cfg.d_model <= 512
+
+
+@dataclasses.dataclass
+class HiddenOut:
+    """Device tensors of one decode_hidden call plus the plan that ran."""
+    x: torch.Tensor     # f32 [positions][B][d]: the residual rows before the final LayerNorm
+    kc: torch.Tensor    # fp16 [layers][B][n_text_ctx][d] self-attention keys (None: not asked)
+    vc: torch.Tensor    # ... values
+    plan: dict          # DecodePlan::describe() as name -> int (pairs / groups: lists)
 
 
 @dataclasses.dataclass

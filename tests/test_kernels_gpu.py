@@ -263,7 +263,8 @@ def test_resunit(gpu, C, k, d, acc, T):
 
 
 @pytest.mark.parametrize("B,Te,D,nsplit", [(2, 1500, 512, 8), (3, 100, 384, 3), (1, 77, 768, 1),
-                                            (4, 1500, 512, 63), (5, 1500, 512, 1), (3, 130, 384, 1)])
+                                            (4, 1500, 512, 63), (5, 1500, 512, 1), (3, 130, 384, 1),
+                                            (2, 1500, 768, 8), (3, 141, 768, 3)])
 def test_cross_attention_absorbed(gpu, B, Te, D, nsplit):
     """softmax_2(qk_h . enc^T) . enc per head vs a float64 torch reference (nsplit 1 at D <=
     512: the kernel writes c itself, no merge launch)."""
@@ -286,7 +287,8 @@ def test_cross_attention_absorbed(gpu, B, Te, D, nsplit):
 
 
 @pytest.mark.parametrize("B,T,H,split", [(3, 1, 8, 0), (2, 37, 6, 0), (64, 448, 8, 0), (2, 512, 8, 0),
-                                         (2, 700, 8, 1), (3, 1000, 8, 1)])
+                                         (2, 700, 8, 1), (3, 1000, 8, 1),
+                                         (2, 64, 12, 0), (2, 65, 12, 0), (5, 448, 12, 0)])
 def test_decode_attention(gpu, B, T, H, split):
     """One query per (b, h) against a KV cache with row stride > d (the decoder's cache
     layout [B][n_ctx][d]); per-head kernel (T <= 512) and the key-split + combine path."""
