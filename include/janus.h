@@ -111,6 +111,42 @@ int janus_vad_set_tensor(janus_vad* v, const char* name, const float* host, int6
 int janus_vad_run(janus_vad* v, const float* pcm, int n_streams, int n_chunks, int chunk_len,
                   int decim, float* ctx_state, float* hc_state, float* prob_out, void* stream);
 
+/*
+ * The same network over whole files (faster-whisper's vad_filter; vad_file.hip): pcm
+ * [device] f32 = the 16 kHz audio of n_streams utterances concatenated, offsets [host]
+ * [n_streams + 1] in samples. Stream s of L_s samples has n_s = L_s / 512 + 1 chunks
+ * (faster-whisper's pad(audio, (0, 512 - len % 512)): a length that is a multiple of 512,
+ * 0 included, gets one whole zero chunk); a sample index >= L_s reads as 0. Every stream
+ * starts from zero state (context 0, h = c = 0: a fresh model per file), and the context of
+ * chunk j is samples [512 j - 64, 512 j) of the SAME stream. prob [device] f32 [sum n_s],
+ * stream-major. n_streams = 0 is a no-op. Everything up to the input half of the LSTM gates
+ * runs batched over all chunks, then one sequential scan per stream, in passes of at most
+ * max_chunks_per_pass chunks per stream (2 KB of context-owned workspace per chunk and
+ * stream; results do not depend on it). 0 = the default: 16384 / n_streams chunks, rounded
+ * down to a multiple of 16 and at least 16, i.e. 32 MB of workspace up to 1024 streams.
+ *
+ * Speech timestamps (services/vad_filter.py, faster-whisper's get_speech_timestamps;
+ * parity unpinned against the package), w = 512, samples at 16 kHz:
+ *   min_speech = 16 min_speech_duration_ms, pad = 16 speech_pad_ms, min_sil = 16
+ *   min_silence_duration_ms, max_speech = 16000 max_speech_duration_s - w - 2 pad,
+ *   min_sil_at_max = 1568, neg_threshold = max(threshold - 0.15, 0.01) unless given.
+ *   State: triggered = false, temp_end = prev_end = next_start = 0. For window i, p:
+ *   1. p >= threshold and temp_end: temp_end = 0; if next_start < prev_end: next_start = w i.
+ *   2. p >= threshold and not triggered: triggered, start = w i; next window.
+ *   3. triggered and w i - start > max_speech: with prev_end set, close at prev_end, then
+ *      untrigger if next_start < prev_end, else open a speech at next_start; zero prev_end,
+ *      next_start, temp_end. Without it, close at w i, zero the three, untrigger; next window.
+ *   4. p < neg_threshold and triggered: temp_end = w i if unset; if w i - temp_end >
+ *      min_sil_at_max: prev_end = temp_end; if w i - temp_end < min_sil: next window; else
+ *      close at temp_end (kept only if end - start > min_speech), zero the three, untrigger.
+ *   An open speech with n_samples - start > min_speech closes at n_samples. Padding: first
+ *   start = max(0, start - pad); between neighbours with sil = next.start - end: sil < 2 pad
+ *   splits it in the middle (end += sil / 2, next.start -= sil / 2), else both move by pad
+ *   (clamped to [0, n_samples]); last end = min(n_samples, end + pad).
+ */
+int janus_vad_probs(janus_vad* v, const float* pcm, const int64_t* offsets, int n_streams,
+                    int max_chunks_per_pass, float* prob, void* stream);
+
 /* -------------------------------------------------------- packet codec --- */
 enum {
   JANUS_VAL_NIL = 0,

@@ -252,6 +252,14 @@ struct VadWeights {
 void silero_vad_launch(const float* pcm, int n_streams, int n_chunks, int chunk_len, int decim,
                        const VadWeights& W, float* ctx_state, float* hc_state, float* prob,
                        hipStream_t s);
+// Whole files (vad_file.hip): pcm [device] = n_streams utterances concatenated, offsets_dev
+// [n_streams + 1] samples, chunk_off_dev [n_streams + 1] = prefix sums of the chunk counts
+// L_s / 512 + 1; every stream from zero state. Runs in passes of pass_chunks chunks per
+// stream: pre [n_streams][pass_chunks][512] and hc_state [n_streams][256] are workspace,
+// max_chunks the chunk count of the longest stream. prob [sum chunks], stream-major.
+void silero_vad_file_launch(const float* pcm, const int64_t* offsets_dev, const int64_t* chunk_off_dev,
+                            int n_streams, int64_t max_chunks, int pass_chunks, const VadWeights& W,
+                            float* pre, float* hc_state, float* prob, hipStream_t s);
 
 // ------------------------------------------------------------------ mel
 void mel_launch(const float* pcm, const int64_t* offsets, int B, const float* basis,

@@ -60,6 +60,7 @@ from .. import _native as nat
 from ..common import wavio
 from ..tokenizer import LANGUAGES, SOT_PREV, TASKS
 from ..whisper import CONFIGS, WhisperEngine, check_beam_args, shared_rows_in_place
+from . import vad_filter as vf
 
 WINDOW_16K = 480000
 N_FRAMES = 3000          # log-mel frames per window (hop 160 @ 16 kHz)
@@ -189,6 +190,13 @@ class TranscriptionInfo:
     # [(code, probability)] by descending probability when the language was detected; None
     # for a given language and for *.en models (as faster-whisper)
     all_language_probs: list = None
+    # vad_filter: seconds of audio kept (= duration without the filter) and the VadOptions used
+    duration_after_vad: float = None
+    vad_options: object = None
+
+    def __post_init__(self):
+        if self.duration_after_vad is None:
+            self.duration_after_vad = self.duration
 
 
 read_wav_16k = wavio.read_wav_16k  # 16-bit PCM WAV -> f32 @ 16 kHz
@@ -433,6 +441,10 @@ class _Stream:
         self.task = "transcribe"
         self.language_pending = False  # still to be detected (language=None)
         self.language_votes = []       # (code, probability) of every window examined so far
+        # vad_filter: the speeches [(start, end)] in samples of the original audio that
+        # ``audio`` was collected from (None: unfiltered) and the seconds of audio decoded
+        self.speech_chunks = None
+        self.duration_after_vad = None if audio16k is None else len(audio16k) / 16000.0
 
     def transcript(self):
         """transcribe_buffer's join of the segments (transcriber.py:59-64)."""
@@ -636,7 +648,8 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
                       word_timestamps: bool = False, prepend_punctuations: str = PREPEND_PUNCTUATIONS,
                       append_punctuations: str = APPEND_PUNCTUATIONS, language=None,
                       task: str = "transcribe", language_detection_segments: int = 1,
-                      language_detection_threshold: float = 0.5):
+                      language_detection_threshold: float = 0.5, vad_filter: bool = False,
+                      vad_parameters=None, vad=None):
     """faster-whisper's seek loop for several 16 kHz utterances at once: every round
     decodes the current window of each unfinished utterance as one GPU batch (per-row
     prompts), then the temperature fallback of the windows whose gates failed
@@ -664,6 +677,14 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     anyway, for the utterances still undecided (_Stream.vote_language: faster-whisper's
     ``language_detection_segments`` / ``language_detection_threshold`` rule); every stream
     carries its language, probability, all_language_probs and its own start sequence.
+    ``vad_filter``: ONE whole-file speech-gate call over all utterances before the features
+    (``vad``: a services.vad.SileroGate -> SileroGate.probs_file / janus_vad_probs; None: the
+    documented energy stand-in janus_vad_energy over 512-sample windows), faster-whisper's
+    speech-timestamp rule under ``vad_parameters`` (a dict or VadOptions), then
+    each utterance is replaced by its collected speech (_Stream.speech_chunks,
+    duration_after_vad), the seek loop runs on that and the segment and word times are
+    restored onto the original audio. An utterance without speech yields no segments. Off
+    (the default), no VAD call is made and nothing differs.
     Returns one _Stream (segments + gate counters) per utterance."""
     check_beam_args(beam_size, length_penalty)
     if beam_size > 1 and speculative:
@@ -674,7 +695,17 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
         raise NotImplementedError("the first temperature must be 0 (faster-whisper's default)")
     tk = engine.tokenizer
     dev = engine.device
-    streams = [_Stream(np.asarray(a, np.float32)) for a in audios]
+    audios = [np.asarray(a, np.float32) for a in audios]
+    speeches = None
+    if vad_filter:
+        opts = vf.as_vad_options(vad_parameters)
+        probs = vf.speech_probabilities(audios, dev, vad) if audios else []
+        speeches = [vf.get_speech_timestamps(p, len(a), opts) for p, a in zip(probs, audios)]
+        audios = [vf.collect_chunks(a, sp) for a, sp in zip(audios, speeches)]
+    streams = [_Stream(a) for a in audios]
+    if speeches is not None:
+        for st, sp in zip(streams, speeches):
+            st.speech_chunks = sp
     multilingual = bool(getattr(tk, "multilingual", False))
     if multilingual:
         if task not in TASKS:
@@ -769,6 +800,9 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
                 al = engine.align(enc, texts, sizes, enc_index=list(range(len(grp))))
             for s, size, c0r, r, nd, nt, a in zip(grp, sizes, first, final, ndec, n_tok, al):
                 advance(tk, s, size, c0r, r, nd, nt, True, a, prepend_punctuations, append_punctuations)
+    for st in streams:
+        if st.speech_chunks:   # times on the collected speech -> times on the original audio
+            st.segments = vf.restore_speech_timestamps(st.segments, vf.SpeechTimestampsMap(st.speech_chunks))
     return streams
 
 
@@ -793,7 +827,7 @@ class WhisperModel:
     ``effective_compute_type`` reports what runs: ``"float16"`` or ``"int8_float16"``."""
 
     def __init__(self, model_size: str, device: str = "auto", compute_type: str = "default",
-                 *, apply_compute_type: bool = False, **_ignored):
+                 *, apply_compute_type: bool = False, vad_weights: dict = None, **_ignored):
         if model_size not in CONFIGS:
             raise ValueError(f"unknown model size {model_size!r}; one of {sorted(CONFIGS)}")
         if device not in DEVICES:
@@ -803,6 +837,19 @@ class WhisperModel:
         self.requested_device, self.requested_compute_type = device, compute_type
         self.engine = WhisperEngine(CONFIGS[model_size], encoder_compute=enc_compute)
         self.stats = {"windows": 0, "needs_fallback": 0, "no_speech_skips": 0, "fallback_decodes": 0}
+        # vad_filter: silero weights (default: JANUS_VAD_DIR; none: the energy stand-in); the
+        # gate is created on the first transcribe(vad_filter=True)
+        self._vad_weights = vad_weights
+        self._vad_gate = None
+
+    def _vad(self):
+        """The SileroGate of vad_filter=True, or None for the energy stand-in."""
+        if self._vad_gate is None:
+            from .vad import SileroGate, load_weights
+            w = self._vad_weights if self._vad_weights is not None else load_weights()
+            if w is not None:
+                self._vad_gate = SileroGate(w)
+        return self._vad_gate
 
     @property
     def is_multilingual(self) -> bool:
@@ -861,13 +908,17 @@ class WhisperModel:
                    prepend_punctuations: str = PREPEND_PUNCTUATIONS,
                    append_punctuations: str = APPEND_PUNCTUATIONS,
                    hallucination_silence_threshold=None, language_detection_segments: int = 1,
-                   language_detection_threshold: float = 0.5, **_ignored):
+                   language_detection_threshold: float = 0.5, vad_filter: bool = False,
+                   vad_parameters=None, **_ignored):
         """faster-whisper's transcribe: ``beam_size`` 1 (greedy, the reference's call) .. 8
         (beam search at T = 0, DESIGN.md §5k), ``length_penalty`` > 0, ``patience`` 1;
         ``max_length``: the decoder's token limit per window (448). ``word_timestamps``: every
         segment carries ``words`` ([Word(start, end, word, probability)]) from the alignment
         pass, with faster-whisper's ``prepend_punctuations`` /
-        ``append_punctuations``; ``hallucination_silence_threshold`` is not built (None only)."""
+        ``append_punctuations``; ``hallucination_silence_threshold`` is not built (None only).
+        ``vad_filter`` / ``vad_parameters`` (a dict or VadOptions): only the speech the gate
+        finds is decoded and every time is restored onto ``audio`` (generate_segments);
+        ``info.duration_after_vad`` is the audio kept, ``info.vad_options`` the options."""
         check_beam_args(beam_size, length_penalty, patience)
         if hallucination_silence_threshold is not None:
             raise NotImplementedError("hallucination_silence_threshold is not supported")
@@ -876,16 +927,19 @@ class WhisperModel:
             audio = read_wav_16k(audio)
         audio = np.ascontiguousarray(audio, dtype=np.float32)
         temps = (float(temperature),) if np.isscalar(temperature) else tuple(temperature)
+        vad_options = vf.as_vad_options(vad_parameters) if vad_filter else None
         st = generate_segments(self.engine, [audio], max_length=max_length, temperatures=temps,
                                best_of=best_of, beam_size=beam_size, length_penalty=length_penalty,
                                word_timestamps=bool(word_timestamps),
                                prepend_punctuations=prepend_punctuations,
                                append_punctuations=append_punctuations, language=language, task=task,
                                language_detection_segments=language_detection_segments,
-                               language_detection_threshold=language_detection_threshold)[0]
+                               language_detection_threshold=language_detection_threshold,
+                               vad_filter=bool(vad_filter), vad_parameters=vad_options,
+                               vad=self._vad() if vad_filter else None)[0]
         self._count(st)
         info = TranscriptionInfo(st.language, st.language_probability, len(audio) / 16000.0,
-                                 st.all_language_probs)
+                                 st.all_language_probs, st.duration_after_vad, vad_options)
         return iter(st.segments), info
 
     def _count(self, st):

@@ -102,6 +102,26 @@ class SileroGate:
                  hc.data_ptr(), prob.data_ptr(), nat.stream_ptr(pcm.device))
         return prob[:S * n].reshape(S, n)
 
+    def probs_file(self, pcm: torch.Tensor, offsets, max_chunks_per_pass: int = 0) -> list:
+        """Whole utterances (faster-whisper's vad_filter): pcm f32 (device) = the 16 kHz audio
+        of S utterances concatenated, offsets [S + 1] (host) in samples -> per utterance the
+        speech probabilities f32 [L // 512 + 1] (numpy) of its 512-sample windows, every
+        utterance from zero state, from ONE janus_vad_probs call. ``max_chunks_per_pass``:
+        windows per utterance and pass of the bounded workspace (0: the default); the result
+        does not depend on it."""
+        assert pcm.is_cuda and pcm.dtype == torch.float32 and pcm.is_contiguous()
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        S = len(offs) - 1
+        if S <= 0:
+            return []
+        assert offs[0] >= 0 and offs[-1] <= pcm.numel() and np.all(np.diff(offs) >= 0)
+        counts = np.diff(offs) // 512 + 1
+        prob = torch.empty(int(counts.sum()), dtype=torch.float32, device=pcm.device)
+        nat.call("janus_vad_probs", self._h, pcm.data_ptr(), offs.ctypes.data, S,
+                 int(max_chunks_per_pass), prob.data_ptr(), nat.stream_ptr(pcm.device))
+        p = prob.cpu().numpy()
+        return [p[e - n:e] for n, e in zip(counts, np.cumsum(counts))]
+
 
 def _energy_prob(chunks: torch.Tensor, decim: int) -> torch.Tensor:
     assert chunks.is_cuda and chunks.dtype == torch.float32 and chunks.is_contiguous()
