@@ -212,13 +212,16 @@ int janus_unpack(const uint8_t* buf, size_t len, janus_mp_node* nodes, size_t ca
  * per utterance). fp16 tensors are passed as uint16_t (IEEE binary16 bits).
  */
 typedef struct {
-  int n_mels;      /* 80 */
+  int n_mels;      /* 80; 128 for the large-v3 family (no other value is accepted) */
   int n_audio_ctx; /* 1500 encoder positions (3000 mel frames) */
-  int d_model;     /* 384 tiny, 512 base */
-  int n_heads;     /* d_model / 64 */
+  int d_model;     /* 384 tiny, 512 base, 768 small, 1280 large-v3 / large-v3-turbo / distil-large-v3 */
+  int n_heads;     /* d_model / 64: up to 20. At 1280 / 20 heads the decode call runs the launch path
+                      (persistent > 0 reports level 0), rows sharing an encoder row are gathered, every
+                      d_model <= 512 fusion is off, and beam search (janus_whisper_decode_beam_ex),
+                      janus_whisper_align and the int8 encoder are refused (non-zero status) */
   int enc_layers;
   int dec_layers;
-  int n_vocab;     /* 51864 for *.en */
+  int n_vocab;     /* 51864 for *.en, 51865 multilingual, 51866 the large-v3 family (100 languages) */
   int n_text_ctx;  /* 448 */
 } janus_whisper_config;
 
@@ -230,15 +233,15 @@ int janus_whisper_destroy(janus_whisper* w);
  * Upload one fp32 parameter [host] by its Hugging Face Whisper name without the
  * "model." prefix (e.g. "encoder.layers.0.fc1.weight"), plus the two front-end
  * constants "mel.basis" [400][416] (periodic-Hann-weighted cos|sin DFT basis, 208
- * bins each) and "mel.filters" [208][80] (slaney mel filters, transposed, zero-padded).
+ * bins each) and "mel.filters" [208][n_mels] (slaney mel filters, transposed, zero-padded).
  */
 int janus_whisper_set_tensor(janus_whisper* w, const char* name, const float* host,
                              int64_t numel);
 /*
- * Log-mel features (faster-whisper FeatureExtractor, n_fft 400, hop 160, 80 mels,
- * 3000 frames) of x[::decim] for each utterance of pcm [device] (offsets [device]
- * int64[B+1]). logmel [device] f32 [B][3000][80] (raw log10 mel, may be NULL), mel
- * [device] fp16 [B][3000][80] (clamped and scaled). The first 30 s window of each clip as
+ * Log-mel features (faster-whisper FeatureExtractor, n_fft 400, hop 160, n_mels = 80 or 128
+ * mels, 3000 frames) of x[::decim] for each utterance of pcm [device] (offsets [device]
+ * int64[B+1]). logmel [device] f32 [B][3000][n_mels] (raw log10 mel, may be NULL), mel
+ * [device] fp16 [B][3000][n_mels] (clamped and scaled). The first 30 s window of each clip as
  * faster-whisper's generate_segments feeds it to the encoder: frames from len(x16) // 160
  * on are 0.0 (pad_or_trim of the content frames), the global max is over the frames that
  * reach the first 30 s + 2 frames of audio (the whole clip when it is <= 30 s).
@@ -248,13 +251,13 @@ int janus_whisper_logmel(janus_whisper* w, const float* pcm, const int64_t* offs
 /*
  * The whole-clip log-mel faster-whisper computes once per transcribe() call
  * (transcriber.py:53-57 -> WhisperModel.transcribe -> FeatureExtractor(audio)): `frames`
- * frames per utterance, mel [device] fp16 [B][frames][80], normalised with the maximum over
+ * frames per utterance, mel [device] fp16 [B][frames][n_mels], normalised with the maximum over
  * every frame of the clip, frames from len(x16) // 160 on 0.0. Its 30 s windows are the
  * slices [seek, seek + min(3000, content - seek)) padded with zeros to 3000 frames.
  */
 int janus_whisper_logmel_frames(janus_whisper* w, const float* pcm, const int64_t* offsets,
                                 int batch, int decim, int frames, uint16_t* mel, void* stream);
-/* Encoder forward: mel [device] fp16 [B][3000][80] -> enc [device] fp16 [B][1500][d]. */
+/* Encoder forward: mel [device] fp16 [B][3000][n_mels] -> enc [device] fp16 [B][1500][d]. */
 int janus_whisper_encode(janus_whisper* w, const uint16_t* mel, int batch, uint16_t* enc,
                          void* stream);
 /*
@@ -630,7 +633,9 @@ int janus_whisper_align(janus_whisper* w, const uint16_t* enc, int n_enc, int n_
  * own — no decoder state slot (KV cache, tokens, graphs, stand) is disturbed, so it may run
  * between two staggered decode calls — and replaces the vocabulary projection by a head that
  * reads n_lang x d x 2 bytes of the embedding. 1 <= n_lang <= 128, lang_begin + n_lang <=
- * n_vocab, else non-zero status (janus_last_error). The context does not know its tokenizer:
+ * n_vocab, else non-zero status (janus_last_error). The 99-language models pass lang_begin
+ * 50259, n_lang 99; the large-v3 family (n_vocab 51866) n_lang 100 — openai/whisper's order
+ * with <|yue|> appended at index 99, token 50358. The context does not know its tokenizer:
  * a *.en model answers too, meaninglessly; callers gate on the model (janus_amd.whisper
  * WhisperEngine.detect_language raises there).
  */

@@ -218,6 +218,19 @@ int janus_sample_gumbel_f32(const uint32_t* seeds, int batch, int pos, int V, fl
  * window, in place.
  */
 int janus_beam_partial_blocks(int V, int K, int max_blocks);
+/*
+ * janus_logits_partial_f16: the vocabulary projection's partials alone, greedy (inv_temp 0) or
+ * sampling (inv_temp = 1 / T > 0 with seeds [batch] device uint32 and the position pos):
+ * K = 384 / 512 / 768 (64-row groups) or 1280 (32-row groups); parts [batch][nblk] x 56 B as
+ * above, nblk = janus_beam_partial_blocks(V, K, max_blocks). target: the token whose raw logit
+ * t_v tracks (-1: none).
+ */
+int janus_logits_partial_f16(const uint16_t* A, const uint16_t* W, int K, int V, int batch,
+                             int eot, int suppress_blank, int blank, int ts_begin,
+                             int no_timestamps, int max_initial_ts, int target,
+                             const uint8_t* smask, const int32_t* row_rules, int max_blocks,
+                             float inv_temp, const uint32_t* seeds, int pos, void* parts,
+                             void* stream);
 int janus_beam_logits_topk_f16(const uint16_t* A, const uint16_t* W, int K, int V, int batch,
                                int eot, int suppress_blank, int blank, int ts_begin,
                                int no_timestamps, int max_initial_ts, const uint8_t* smask,

@@ -128,6 +128,8 @@ SIGNATURES = {
     "janus_beam_partial_blocks": [_I32, _I32, _I32],
     "janus_beam_logits_topk_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P,
                                    _I32, _P, _P, _I32, _P, _P, _P, _P, _P],
+    "janus_logits_partial_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P,
+                                 _I32, _F32, _P, _I32, _P, _P],
     "janus_beam_step": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P,
                         _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "janus_beam_reorder_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],

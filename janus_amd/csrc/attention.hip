@@ -366,7 +366,7 @@ __global__ __launch_bounds__(512) void decode_combine_kernel(const float* __rest
 constexpr int kHeadWaves = 8;
 constexpr int kHeadRounds = 8;                               // key groups per wave
 constexpr int kHeadKeys = 8 * kHeadWaves * kHeadRounds;      // 512
-constexpr int kHeadMaxHeads = 16;                            // grid.x; no per-head storage
+constexpr int kHeadMaxHeads = 20;                            // grid.x; no per-head storage
 
 // NR: key rounds actually holding keys (ceil(Tkv / 64)): the rounds past the cache end
 // only loaded the clamped last row and added p = 0 — dropping them changes no bit.
@@ -485,7 +485,7 @@ void decode_attention_split_launch(const _Float16* q, int64_t q_bs, const _Float
                                    const int32_t* roff, int max_roff) {
   // the per-head kernel (grid H x B) sizes nothing by H; the split-key kernels below hold
   // kMaxHeads heads per block in LDS and 8-dim slices of one key row in 64 lanes
-  JANUS_CHECK(H >= 1 && H <= kHeadMaxHeads, "decode attention: at most 16 heads (d <= 1024)");
+  JANUS_CHECK(H >= 1 && H <= kHeadMaxHeads, "decode attention: at most 20 heads (d <= 1280)");
   if (B <= 0 || Tkv <= 0) return;
   const int tmax = Tkv + (roff ? max_roff : 0);
   JANUS_CHECK(!roff || tmax <= kHeadKeys, "decode attention: staggered rows need <= 512 keys");

@@ -132,6 +132,8 @@ static void plan_rows(DecodePlan& P, const janus_whisper_config& c, const janus_
     for (int b = f0; b < f1; ++b) JANUS_CHECK(h_roff[b] == 0, "decode: fresh rows must be contiguous");
   }
   if (beam) {
+    JANUS_CHECK(c.d_model <= 768, "decode: beam search needs d_model <= 768 (the vocabulary projection has no "
+                                  "beam partials at 1280)");
     JANUS_CHECK(beam->k >= 1 && beam->k <= kBeamMax && B % beam->k == 0, "decode: beam_size must be 1 .. 8");
     JANUS_CHECK(!stagger, "decode: beam search does not take staggered rows (pos_offset)");
     JANUS_CHECK(!(smp && smp->temperature > 0.f), "decode: beam search runs at temperature 0");

@@ -370,6 +370,7 @@ void rules_init_launch(RowRules* rules, int B, hipStream_t s) {
 // waves per logits block (16 waves — about one tile per wave — measured 4x slower:
 // 114.7 vs 28.8 us per launch)
 constexpr int lg_waves(int /*K*/) { return 8; }
+int logits_row_group(int K) { return K > 768 ? 32 : 64; }
 int logits_partial_blocks(int V, int K, int max_blocks) {
   const int cap = max_blocks > 0 ? max_blocks : 256;  // one per CU of a whole MI355X
   return std::max(1, std::min(cap, ((V + 15) / 16 + lg_waves(K) - 1) / lg_waves(K)));
@@ -396,7 +397,11 @@ int logits_partial_blocks(int V, int K, int max_blocks) {
 // BEAM (beam search, greedy keys): the row's kBeamTop best allowed entries of this block's
 // columns ride along (BeamTop: every allowed token / the allowed timestamps), kept per lane
 // = row in sorted registers and merged over the 8 waves after the statistics.
-template <int NKS, int NB, bool SAMPLE, bool BEAM = false>  // K / 32
+// MT: 16-row m-tiles of A per row group (RG = 16 MT rows). 4 up to K = 768: all 64 rows
+// of a group in LDS. K = 1280 (the large-v3 family): 64 rows x 1296 halves are 166 KB, more
+// than a CU's 160 KB, so a group is 32 rows (MT = 2: 83 KB of A, 17 KB of patches) and lanes
+// 32 - 63 idle in the statistics pass; the weights are read once per 32-row group.
+template <int NKS, int NB, bool SAMPLE, bool BEAM = false, int MT = 4>  // K / 32
 __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel(
     const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W, int V, int B,
     DecodeRules R, const uint8_t* __restrict__ smask, const RowRules* __restrict__ rules,
@@ -406,10 +411,12 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
     BeamTop* __restrict__ tops) {
   extern __shared__ __attribute__((aligned(16))) _Float16 lg_smem[];
   dec_wave_prio();
-  // row group blockIdx.y: rows [64 y, 64 y + 64) of the call (one launch for every group:
+  // row group blockIdx.y: rows [RG y, RG y + RG) of the call (one launch for every group:
   // a group's blocks start while the previous group's last blocks drain)
+  constexpr int RG = 16 * MT;
+  static_assert(!BEAM || MT == 4, "the beam merge is laid out for 64-row groups");
   {
-    const int r0 = (int)blockIdx.y * 64;
+    const int r0 = (int)blockIdx.y * RG;
     A += (int64_t)r0 * lda;
     rules += r0;
     parts += (int64_t)r0 * gridDim.x;
@@ -417,14 +424,14 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
     if (seeds) seeds += r0;
     if (rinv) rinv += r0;
     if (BEAM) tops += (int64_t)r0 * gridDim.x;
-    B = min(64, B - r0);
+    B = min(RG, B - r0);
   }
   constexpr int K = NKS * 32;
   constexpr int kLgWaves = lg_waves(K);
   constexpr int AP = K + 16;  // row pitch (halves): 16*AP bytes with AP/8 % 4 == 2 -> conflict-free
-  _Float16* sA = lg_smem;                                            // [64][AP]
-  float* sT = reinterpret_cast<float*>(sA + 64 * AP);                // [waves][64][17]
-  RowRules* sR = reinterpret_cast<RowRules*>(sT + kLgWaves * 64 * 17);  // [64]
+  _Float16* sA = lg_smem;                                            // [RG][AP]
+  float* sT = reinterpret_cast<float*>(sA + RG * AP);                // [waves][RG][17]
+  RowRules* sR = reinterpret_cast<RowRules*>(sT + kLgWaves * RG * 17);  // [64]
   const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
   // the first tile's weights and suppress-mask bytes are issued before A is staged (they
   // do not depend on it); later tiles' loads are issued before the previous epilogue
@@ -446,26 +453,42 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
 #pragma unroll
   for (int u = 0; u < NB; ++u)
     if (tile0 + u * stride < ntiles) LG_LOAD(u, tile0 + u * stride);
-  if (lnx) {  // A = the decoder's final LayerNorm of x, computed here (one wave per row)
+  bool ln_here = false;
+  if constexpr (K <= 1024) ln_here = lnx != nullptr;  // (ln_rows_wave: d <= 1024; the launcher checks)
+  if (ln_here) {  // A = the decoder's final LayerNorm of x, computed here (one wave per row)
     // wave w: rows w + 8j (j < 8), all loads up front
-    ln_rows_wave<(K + 255) / 256, 64 / kLgWaves>(lnx, ldx, w, kLgWaves, B, ln_g, ln_b, sA, w, AP, K,
-                                                 1e-5f, lane);
+    if constexpr (K <= 1024)
+      ln_rows_wave<(K + 255) / 256, RG / kLgWaves>(lnx, ldx, w, kLgWaves, B, ln_g, ln_b, sA, w, AP, K,
+                                                   1e-5f, lane);
   } else {
-    for (int i = tid; i < 64 * (K / 8); i += kLgWaves * 64) {
+    for (int i = tid; i < RG * (K / 8); i += kLgWaves * 64) {
       const int r = i / (K / 8), c8 = (i % (K / 8)) * 8;
       uint4 v = make_uint4(0, 0, 0, 0);
       if (r < B) v = *reinterpret_cast<const uint4*>(A + (int64_t)r * lda + c8);
       *reinterpret_cast<uint4*>(sA + r * AP + c8) = v;
     }
   }
-  if (tid < 64) {
+  if constexpr (MT != 4) {
+    // (every field set, pad[] too: the half-initialised struct below goes through 12 bytes of
+    // scratch per lane, which the instantiations up to K = 768 keep as compiled)
+    static_assert(sizeof(RowRules) == 32, "two 16-byte halves");
+    if (tid < 64) {   // (rules: 32-byte rows of a device allocation; sR: 16-byte aligned in LDS)
+      int4 lo = make_int4(0, 0, 0, -1), hi = make_int4(-1, 0, 0, 0);   // ts_floor, last_stamp: none
+      if (tid < B) {
+        const int4* src = reinterpret_cast<const int4*>(rules + tid);
+        lo = src[0]; hi = src[1];
+      }
+      int4* dst = reinterpret_cast<int4*>(sR + tid);
+      dst[0] = lo; dst[1] = hi;
+    }
+  } else if (tid < 64) {
     RowRules rr;
     if (tid < B) rr = rules[tid];
     else { rr.sample_begin = 0; rr.suppress_all_ts = rr.suppress_text = 0; rr.ts_floor = -1; rr.last_stamp = -1; }
     sR[tid] = rr;
   }
   __syncthreads();
-  float* patch = sT + w * 64 * 17;
+  float* patch = sT + w * RG * 17;
   const int lr = lane & 15, kc8 = 8 * (lane >> 4);
   RowRules rr;  // lane = row in the statistics pass (fields copied: no scratch for pad[])
   rr.sample_begin = sR[lane].sample_begin; rr.suppress_all_ts = sR[lane].suppress_all_ts;
@@ -506,31 +529,31 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
     const int tile = tb + u * stride;
     if (tile >= ntiles) break;  // wave-uniform
     const int col0 = phys(tile) * 16;
-    f32x4 acc[4];
+    f32x4 acc[MT];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) acc[m] = zero_f32x4();
+    for (int m = 0; m < MT; ++m) acc[m] = zero_f32x4();
     // A fragments of k-step ks+1 read while k-step ks's MFMAs run (left to the compiler,
     // every ds_read was followed by an lgkmcnt(0) wait and one MFMA: 64 exposed LDS round
     // trips per tile)
-    half8 af[2][4];
+    half8 af[2][MT];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) af[0][m] = *reinterpret_cast<const half8*>(sA + (16 * m + lr) * AP + kc8);
+    for (int m = 0; m < MT; ++m) af[0][m] = *reinterpret_cast<const half8*>(sA + (16 * m + lr) * AP + kc8);
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
       if (ks + 1 < NKS) {
 #pragma unroll
-        for (int m = 0; m < 4; ++m)
+        for (int m = 0; m < MT; ++m)
           af[(ks + 1) & 1][m] = *reinterpret_cast<const half8*>(sA + (16 * m + lr) * AP + 32 * (ks + 1) + kc8);
       }
       // keep the reads above the MFMAs (the scheduler otherwise sinks each read to just
       // before its MFMA to save registers, re-serialising the loop)
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int m = 0; m < 4; ++m) acc[m] = mfma16(af[ks & 1][m], bw[u][ks], acc[m]);
+      for (int m = 0; m < MT; ++m) acc[m] = mfma16(af[ks & 1][m], bw[u][ks], acc[m]);
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
-    for (int m = 0; m < 4; ++m)
+    for (int m = 0; m < MT; ++m)
 #pragma unroll
       for (int r = 0; r < 4; ++r) patch[(16 * m + 4 * (lane >> 4) + r) * 17 + lr] = acc[m][r];
     const uint4 smc = sm16[u];
@@ -539,6 +562,7 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
     // wave-private patch: the wave's own stores are visible to its loads in order
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
     const int row = lane;
+    const int prow = RG < 64 ? min(row, RG - 1) : row;  // lanes past the group read its last row (unused)
     float t_all = -INFINITY, t_text = -INFINITY, t_ts = -INFINITY, t_raw = -INFINITY;
     float vals[16];
     unsigned okm = 0;
@@ -555,7 +579,7 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
       const bool row_ok = row < B && !(R.ts_begin >= 0 && ((rr.suppress_text && col0 < R.eot) || rr.sample_begin));
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
-        const float v = patch[row * 17 + c];
+        const float v = patch[prow * 17 + c];
         vals[c] = v;
         t_raw = fmaxf(t_raw, v);
         if (col0 + c == R.target) t_v = v;
@@ -594,7 +618,7 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
         const int t = col0 + c;
-        const float v = patch[row * 17 + c];
+        const float v = patch[prow * 17 + c];
         vals[c] = v;
         if (t < V) t_raw = fmaxf(t_raw, v);
         if (t == R.target) t_v = v;
@@ -636,20 +660,21 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
   }
   // merge the 8 waves' statistics per row (wave order), one partial per (row, block)
   __syncthreads();  // every wave is done with its patch: reuse sT for the wave partials
-  LogitPart* wp = reinterpret_cast<LogitPart*>(sT);  // [kLgWaves][64]
-  {
+  LogitPart* wp = reinterpret_cast<LogitPart*>(sT);  // [kLgWaves][RG]
+  static_assert(sizeof(LogitPart) <= 17 * 4, "the wave partials fit the patches");
+  if (lane < RG) {
     LogitPart p;
     p.m_all = m_all; p.s_all = s_all; p.m_text = m_text; p.m_ts = m_ts; p.s_ts = s_ts;
     p.b_all_v = ba_v; p.b_all_i = ba_i; p.b_ts_v = bt_v; p.b_ts_i = bt_i;
     p.b_all_r = SAMPLE ? ba_r : ba_v; p.b_ts_r = SAMPLE ? bt_r : bt_v;
     p.t_v = t_v; p.m_raw = m_raw; p.s_raw = s_raw;
-    wp[w * 64 + lane] = p;
+    wp[w * RG + lane] = p;
   }
   __syncthreads();
   if (w == 0 && lane < B) {
     LogitPart q = wp[lane];
     for (int k = 1; k < kLgWaves; ++k) {
-      const LogitPart p = wp[k * 64 + lane];
+      const LogitPart p = wp[k * RG + lane];
       float mo;
       q.s_all = lse_merge(q.m_all, q.s_all, p.m_all, p.s_all, &mo); q.m_all = mo;
       q.s_ts = lse_merge(q.m_ts, q.s_ts, p.m_ts, p.s_ts, &mo); q.m_ts = mo;
@@ -715,20 +740,25 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
                            const float* ln_g, const float* ln_b, int max_blocks,
                            const uint32_t* seeds, int pos, const float* row_inv_temp, BeamTop* tops) {
   JANUS_CHECK(!tops || !(R.inv_temp > 0.f), "logits: the beam partials are greedy only");
-  JANUS_CHECK(K == 384 || K == 512 || K == 768, "logits: K (d_model) must be 384, 512 or 768");
+  JANUS_CHECK(K == 384 || K == 512 || K == 768 || K == 1280, "logits: K (d_model) must be 384, 512, 768 or 1280");
+  // K = 1280: 32-row groups (64 rows of A do not fit a CU's LDS), greedy and sampling only
+  const bool k1280 = K == 1280;
+  const int rg = logits_row_group(K);
+  JANUS_CHECK(!k1280 || (!tops && !lnx), "logits: K = 1280 has no beam partials and no LayerNorm prologue");
   const bool sample = R.inv_temp > 0.f;
   JANUS_CHECK(!sample || seeds, "logits: sampling needs per-row seeds");
   const int ntiles = (V + 15) / 16;
   const int nw = lg_waves(K);
-  const size_t lds = (size_t)64 * (K + 16) * 2 + (size_t)nw * 64 * 17 * 4 + 64 * sizeof(RowRules);
+  const size_t lds = (size_t)rg * (K + 16) * 2 + (size_t)nw * rg * 17 * 4 + 64 * sizeof(RowRules);
   auto kern = tops ? (K == 384 ? logits_partial_kernel<12, 1, false, true> : K == 512 ? logits_partial_kernel<16, 1, false, true>
                                                                         : logits_partial_kernel<24, 1, false, true>)
               : sample ? (K == 384 ? logits_partial_kernel<12, 1, true> : K == 512 ? logits_partial_kernel<16, 1, true>
                                                                           : logits_partial_kernel<24, 1, true>)
                        : (K == 384 ? logits_partial_kernel<12, 1, false> : K == 512 ? logits_partial_kernel<16, 1, false>
                                                                            : logits_partial_kernel<24, 1, false>);
-  static bool attr[9] = {false, false, false, false, false, false, false, false, false};
-  const int ai = (K == 384 ? 0 : K == 512 ? 1 : 2) + (tops ? 6 : sample ? 3 : 0);
+  if (k1280) kern = sample ? logits_partial_kernel<40, 1, true, false, 2> : logits_partial_kernel<40, 1, false, false, 2>;
+  static bool attr[11] = {false, false, false, false, false, false, false, false, false, false, false};
+  const int ai = k1280 ? 9 + (int)sample : (K == 384 ? 0 : K == 512 ? 1 : 2) + (tops ? 6 : sample ? 3 : 0);
   if (!attr[ai]) {
     JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024));
@@ -751,8 +781,8 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
     if (rem > 0 && nspec > 0 && rem + nspec + (R.blank >= 0 ? 1 + R.blank / 16 : 0) <= stride)
       rot = ((s0 - rem) % ntiles + ntiles) % ntiles;
   }
-  // 64 rows per row group (blockIdx.y), every group in one launch
-  kern<<<dim3(grid, (B + 63) / 64), nw * 64, lds, s>>>(A, lda, W, V, B, R, smask, rules, parts, ntiles, lnx, ldx,
+  // 64 (K = 1280: 32) rows per row group (blockIdx.y), every group in one launch
+  kern<<<dim3(grid, (B + rg - 1) / rg), nw * 64, lds, s>>>(A, lda, W, V, B, R, smask, rules, parts, ntiles, lnx, ldx,
                                                       ln_g, ln_b, rot, seeds, pos,
                                                       sample ? row_inv_temp : nullptr, tops);
   JANUS_LAUNCH_CHECK();

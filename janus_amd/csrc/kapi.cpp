@@ -282,6 +282,28 @@ extern "C" int janus_beam_logits_topk_f16(const uint16_t* A, const uint16_t* W, 
   });
 }
 
+// The vocabulary projection's partials alone (greedy, or sampling with seeds / inv_temp > 0):
+// parts [batch][nblk] LogitPart, nblk = janus_beam_partial_blocks(V, K, max_blocks).
+extern "C" int janus_logits_partial_f16(const uint16_t* A, const uint16_t* W, int K, int V, int batch,
+                                        int eot, int suppress_blank, int blank, int ts_begin,
+                                        int no_timestamps, int max_initial_ts, int target,
+                                        const uint8_t* smask, const int32_t* row_rules, int max_blocks,
+                                        float inv_temp, const uint32_t* seeds, int pos, void* parts,
+                                        void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(A && W && smask && row_rules && parts, "null argument");
+    JANUS_CHECK(batch >= 1 && batch <= kSkinnyMaxRows, "logits_partial: 1 <= batch <= 512");
+    static_assert(sizeof(RowRules) == 32 && sizeof(LogitPart) == 56, "ABI sizes");
+    DecodeRules R = beam_rules(eot, suppress_blank, blank, ts_begin, no_timestamps, max_initial_ts);
+    R.target = target;
+    R.inv_temp = inv_temp > 0.f ? inv_temp : 0.f;
+    logits_partial_launch(reinterpret_cast<const _Float16*>(A), K, reinterpret_cast<const _Float16*>(W), K, V,
+                          batch, R, smask, reinterpret_cast<const RowRules*>(row_rules),
+                          static_cast<LogitPart*>(parts), (hipStream_t)stream, nullptr, 0, nullptr, nullptr,
+                          max_blocks, seeds, pos, nullptr, nullptr);
+  });
+}
+
 extern "C" int janus_beam_step(const void* parts, const void* tops, int nblk, int eot, int suppress_blank,
                                int blank, int ts_begin, int no_timestamps, int max_initial_ts,
                                int32_t* row_rules, int32_t* tokens, int ld, int pos, int32_t* done,

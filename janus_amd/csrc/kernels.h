@@ -264,7 +264,7 @@ void silero_vad_file_launch(const float* pcm, const int64_t* offsets_dev, const 
 // ------------------------------------------------------------------ mel
 void mel_launch(const float* pcm, const int64_t* offsets, int B, const float* basis,
                 const float* filters, float* logmel, uint32_t* maxkey, int n_frames_out,
-                int decim, hipStream_t s);
+                int decim, hipStream_t s, int n_mels = 80);  // filters [208][n_mels], n_mels 80 | 128
 void mel_normalize_launch(const float* logmel, const uint32_t* maxkey, _Float16* out,
                           const int64_t* offsets, int decim, int B, int frames, int n_mels,
                           int out_ld, hipStream_t s);

@@ -3,7 +3,8 @@
 //   x16 = x48[::3]                        (transcriber.py:51, fused as a strided read)
 //   frames: n_fft 400, hop 160, center=True (reflect), periodic Hann; the waveform is
 //           zero-padded on the right (faster-whisper pads 30 s of zeros)
-//   P = |rFFT|^2 (201 bins), mel = P @ filters[201x80] (slaney), log10(max(mel,1e-10))
+//   P = |rFFT|^2 (201 bins), mel = P @ filters[201 x n_mels] (slaney; n_mels = 80, or 128
+//   for the large-v3 family), log10(max(mel,1e-10))
 //   then (in mel_normalize) max(x, global_max - 8), (x + 4) / 4.
 // The 400-point DFT is a GEMM [frames x 400] x [400 x 416] (Hann folded into a
 // cos|sin basis) on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32, fp32 accumulate);
@@ -18,7 +19,6 @@ namespace janus {
 constexpr int kNfft = 400, kHop = 160;
 constexpr int kBinPad = 208;                 // 13 tiles of 16
 constexpr int kNB = 2 * kBinPad;             // basis columns: cos | sin
-constexpr int kMels = 80;
 constexpr int kFT = 64;                      // frames per block
 constexpr int kXRow = 162;                   // LDS pitch per hop of samples
 constexpr int kXRows = (kFT * kHop + kNfft - kHop) / kHop + 1;  // 66 rows
@@ -41,6 +41,8 @@ constexpr int kKG = 10;                      // DFT k-steps per basis prefetch g
 constexpr int kNG = kNfft / 4 / kKG;         // 10 groups
 static_assert(kNG * kKG * 4 == kNfft && kNG % 2 == 0, "basis prefetch groups");
 
+// NMT: 16-bin mel tiles of the filter step (5: 80 bins, 8: 128 bins); filtT is [kBinPad][16 NMT]
+template <int NMT>
 __global__ __launch_bounds__(256, 3) void mel_kernel(const float* __restrict__ pcm,
                                                   const int64_t* __restrict__ offsets,
                                                   const float* __restrict__ basis,
@@ -129,22 +131,23 @@ __global__ __launch_bounds__(256, 3) void mel_kernel(const float* __restrict__ p
   }
   __syncthreads();
 
-  // mel projection: wave w -> frames 16w..16w+15, all 5 mel tiles
-  f32x4 mel[5];
+  // mel projection: wave w -> frames 16w..16w+15, all NMT mel tiles
+  constexpr int kMels = 16 * NMT;
+  f32x4 mel[NMT];
 #pragma unroll
-  for (int t = 0; t < 5; ++t) mel[t] = zero_f32x4();
+  for (int t = 0; t < NMT; ++t) mel[t] = zero_f32x4();
   for (int kk = 0; kk < kBinPad / 4; ++kk) {
     const int bin = kk * 4 + (lane >> 4);
     const float av = ps[(w * 16 + (lane & 15)) * kPS + bin];
 #pragma unroll
-    for (int t = 0; t < 5; ++t) {
+    for (int t = 0; t < NMT; ++t) {
       const float bv = filtT[bin * kMels + t * 16 + (lane & 15)];
       mel[t] = mfma_f32(av, bv, mel[t]);
     }
   }
   float mx = -INFINITY;
 #pragma unroll
-  for (int t = 0; t < 5; ++t)
+  for (int t = 0; t < NMT; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int fr = f0 + w * 16 + 4 * (lane >> 4) + r;
@@ -167,6 +170,7 @@ __global__ __launch_bounds__(256, 3) void mel_kernel(const float* __restrict__ p
 // of the whole clip's log-mel (content frames only: segment_size = min(3000,
 // content_frames - seek)) and pads it to 3000 frames with zeros (pad_or_trim), so a window
 // past the end of the audio holds 0.0 there, not the log-mel of silence.
+template <int kMels>
 __global__ void mel_normalize_kernel(const float* __restrict__ logmel,
                                      const uint32_t* __restrict__ maxkey, _Float16* __restrict__ out,
                                      const int64_t* __restrict__ offsets, int decim,
@@ -186,26 +190,36 @@ __global__ void mel_normalize_kernel(const float* __restrict__ logmel,
 
 void mel_launch(const float* pcm, const int64_t* offsets, int B, const float* basis,
                 const float* filters, float* logmel, uint32_t* maxkey, int n_frames_out,
-                int decim, hipStream_t s) {
+                int decim, hipStream_t s, int n_mels) {
   JANUS_CHECK(decim >= 1, "mel: decimation must be >= 1");
+  JANUS_CHECK(n_mels == 80 || n_mels == 128, "mel: 80 or 128 bins");
   if (B <= 0) return;
   // frames whose window reaches audio: up to index 3001 for a 30 s input
   const int n_frames_max = n_frames_out + 2;
   JANUS_HIP(hipMemsetAsync(maxkey, 0, sizeof(uint32_t) * B, s));
   dim3 grid((n_frames_max + kFT - 1) / kFT, B);
-  mel_kernel<<<grid, 256, 0, s>>>(pcm, offsets, basis, filters, logmel, maxkey, n_frames_out,
-                                  n_frames_max, decim);
+  if (n_mels == 80)
+    mel_kernel<5><<<grid, 256, 0, s>>>(pcm, offsets, basis, filters, logmel, maxkey, n_frames_out,
+                                       n_frames_max, decim);
+  else
+    mel_kernel<8><<<grid, 256, 0, s>>>(pcm, offsets, basis, filters, logmel, maxkey, n_frames_out,
+                                       n_frames_max, decim);
   JANUS_LAUNCH_CHECK();
 }
 
 void mel_normalize_launch(const float* logmel, const uint32_t* maxkey, _Float16* out,
                           const int64_t* offsets, int decim, int B, int frames, int n_mels,
                           int out_ld, hipStream_t s) {
-  JANUS_CHECK(n_mels == kMels, "mel: 80 bins only");
-  const int64_t total = (int64_t)B * frames * kMels;
+  JANUS_CHECK(n_mels == 80 || n_mels == 128, "mel: 80 or 128 bins");
+  const int64_t total = (int64_t)B * frames * n_mels;
   if (total == 0) return;
-  mel_normalize_kernel<<<(unsigned)cdiv(total, 256), 256, 0, s>>>(logmel, maxkey, out, offsets,
-                                                                   decim, frames, out_ld, total);
+  JANUS_CHECK(cdiv(total, 256) < (1ll << 31), "mel: too many frames");
+  if (n_mels == 80)
+    mel_normalize_kernel<80><<<(unsigned)cdiv(total, 256), 256, 0, s>>>(logmel, maxkey, out, offsets,
+                                                                         decim, frames, out_ld, total);
+  else
+    mel_normalize_kernel<128><<<(unsigned)cdiv(total, 256), 256, 0, s>>>(logmel, maxkey, out, offsets,
+                                                                          decim, frames, out_ld, total);
   JANUS_LAUNCH_CHECK();
 }
 

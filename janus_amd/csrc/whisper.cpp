@@ -251,7 +251,7 @@ extern "C" int janus_whisper_create(const janus_whisper_config* cfg, janus_whisp
     JANUS_CHECK(cfg && out, "null argument");
     JANUS_CHECK(cfg->d_model % 64 == 0 && cfg->n_heads * 64 == cfg->d_model,
                 "whisper: head_dim must be 64");
-    JANUS_CHECK(cfg->n_mels == 80, "whisper: 80 mel bins supported");
+    JANUS_CHECK(cfg->n_mels == 80 || cfg->n_mels == 128, "whisper: 80 or 128 mel bins supported");
     auto* w = new janus_whisper();
     w->cfg = *cfg;
     *out = w;
@@ -279,17 +279,18 @@ extern "C" int janus_whisper_set_tensor(janus_whisper* w, const char* name, cons
 
 static void logmel_frames(janus_whisper* w, const float* pcm, const int64_t* offsets, int batch,
                           int decim, int frames, float* logmel, uint16_t* mel, hipStream_t s) {
+  const int nm = w->cfg.n_mels;
   float* lm = logmel;
   if (!lm) {
-    w->ws_logmel.ensure(sizeof(float) * (int64_t)batch * frames * 80);
+    w->ws_logmel.ensure(sizeof(float) * (int64_t)batch * frames * nm);
     lm = w->ws_logmel.as<float>();
   }
   w->ws_maxkey.ensure(sizeof(uint32_t) * (batch > 0 ? batch : 1));
   mel_launch(pcm, offsets, batch, w->params.get("mel.basis", 400 * 416),
-             w->params.get("mel.filters", 208 * 80), lm, w->ws_maxkey.as<uint32_t>(), frames,
-             decim, s);
+             w->params.get("mel.filters", 208 * nm), lm, w->ws_maxkey.as<uint32_t>(), frames,
+             decim, s, nm);
   mel_normalize_launch(lm, w->ws_maxkey.as<uint32_t>(), reinterpret_cast<_Float16*>(mel), offsets,
-                       decim, batch, frames, 80, 80, s);
+                       decim, batch, frames, nm, nm, s);
 }
 
 extern "C" int janus_whisper_logmel(janus_whisper* w, const float* pcm, const int64_t* offsets,
@@ -308,7 +309,7 @@ extern "C" int janus_whisper_logmel_frames(janus_whisper* w, const float* pcm,
                                            int frames, uint16_t* mel, void* stream) {
   return guarded([&] {
     JANUS_CHECK(w && pcm && offsets && mel, "null argument");
-    JANUS_CHECK(frames >= 1 && (int64_t)batch * frames * 80 < (1ll << 40), "bad frame count");
+    JANUS_CHECK(frames >= 1 && (int64_t)batch * frames * w->cfg.n_mels < (1ll << 40), "bad frame count");
     std::lock_guard<std::mutex> lk(w->mu);
     logmel_frames(w, pcm, offsets, batch, decim, frames, nullptr, mel, (hipStream_t)stream);
   });

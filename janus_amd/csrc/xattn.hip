@@ -64,15 +64,18 @@ void xattn_absorb(const float* wq, const float* bq, const float* wk, int D, int 
   JANUS_LAUNCH_CHECK();
 }
 
-template <int D, int CH, bool PAIR = false, bool DIRECT = false, bool PF2 = false, bool ROWLD = false>
-__global__ __launch_bounds__(CH * 8, PF2 ? 1 : 2) void xattn_kernel(
+// HG: heads per block (xattn_body.h; grid.z head groups), D = 1280 only — one block per CU there
+// (88.6 KB of LDS; the 60 + 20 + 20 half8 / f32x4 of Q, E and C fragments need the registers)
+template <int D, int CH, bool PAIR = false, bool DIRECT = false, bool PF2 = false, bool ROWLD = false, int HG = 0>
+__global__ __launch_bounds__(CH * 8, (PF2 || HG) ? 1 : 2) void xattn_kernel(
     const _Float16* __restrict__ qk, const _Float16* __restrict__ enc, int Te, int H, int kps,
     float* __restrict__ part_c, float* __restrict__ part_ml, const int4* __restrict__ pairs,
     _Float16* __restrict__ out = nullptr, int rev = 0) {
   extern __shared__ __attribute__((aligned(16))) _Float16 smem[];
   dec_wave_prio();
-  xattn_body<D, CH, PAIR, DIRECT, PF2, false, ROWLD>(qk, enc, Te, H, kps, part_c, part_ml, pairs, out,
-                                                     blockIdx.x, gridDim.x, blockIdx.y, smem, rev != 0);
+  xattn_body<D, CH, PAIR, DIRECT, PF2, false, ROWLD, HG>(qk, enc, Te, H, kps, part_c, part_ml, pairs, out,
+                                                         blockIdx.x, gridDim.x, blockIdx.y, smem, rev != 0,
+                                                         HG ? (int)blockIdx.z : 0);
 }
 
 // GROUP (r04): up to 2*NMT decoder rows attending to the same encoder row — the best_of = 5
@@ -554,12 +557,14 @@ void xattn_rows_launch(const _Float16* qk, const _Float16* enc, int Te, int D, i
 }
 
 // c[b][h*D + j] = sum_s 2^(m_s - M) C_s[h][j] / sum_s 2^(m_s - M) l_s   (fp16)
+constexpr int kXCombHeads = 20;  // heads of one row (HM: the LDS weights per head and split)
+template <int HM>
 __global__ __launch_bounds__(256) void xattn_combine_kernel(const float* __restrict__ part_c,
                                                             const float* __restrict__ part_ml,
                                                             int nsplit, int H, int D,
                                                             _Float16* __restrict__ out) {
-  __shared__ float sw[16][64];  // per (head, split) weight, then 1/L in [h][63]... (nsplit <= 63)
-  __shared__ float sinv[16];
+  __shared__ float sw[HM][64];  // per (head, split) weight, then 1/L in [h][63]... (nsplit <= 63)
+  __shared__ float sinv[HM];
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* pml = part_ml + (int64_t)b * nsplit * H * 2;
   if (tid < H) {
@@ -789,28 +794,55 @@ static void xattn_cfg(const _Float16* qk, const _Float16* enc, int B, int Te, in
   JANUS_LAUNCH_CHECK();
 }
 
+static void xattn_combine_rows(const float* part_c, const float* part_ml, int nsplit, int B, int H, int D,
+                               _Float16* out, hipStream_t s) {
+  if (H <= 16) xattn_combine_kernel<16><<<B, 256, 0, s>>>(part_c, part_ml, nsplit, H, D, out);
+  else xattn_combine_kernel<kXCombHeads><<<B, 256, 0, s>>>(part_c, part_ml, nsplit, H, D, out);
+}
+
 // The split merge on its own (what xattn_launch(combine = true) runs after its kernel): for
 // partials written by xattn_rows_launch. The same kernel choice, so the same bits.
 void xattn_combine_launch(const float* part_c, const float* part_ml, int nsplit, int B, int H, int D,
                           _Float16* out, hipStream_t s) {
-  JANUS_CHECK(H >= 1 && H <= 16 && nsplit >= 1 && nsplit <= 63 && D % 4 == 0,
-              "xattn combine: H <= 16, 1..63 key splits");
+  JANUS_CHECK(H >= 1 && H <= kXCombHeads && nsplit >= 1 && nsplit <= 63 && D % 4 == 0,
+              "xattn combine: H <= 20, 1..63 key splits");
   if (B <= 0) return;
   if (nsplit <= kXCombMax && D <= 512)
     xattn_combine_wide_kernel<<<dim3(H, B), 128, 0, s>>>(part_c, part_ml, nsplit, H, D, out);
   else
-    xattn_combine_kernel<<<B, 256, 0, s>>>(part_c, part_ml, nsplit, H, D, out);
+    xattn_combine_rows(part_c, part_ml, nsplit, B, H, D, out, s);
   JANUS_LAUNCH_CHECK();
 }
 
 bool xattn_supported(int D, int H) {
-  return H * 64 == D && H <= 16 && (D == 384 || D == 512 || D == 768);
+  return H * 64 == D && H <= kXCombHeads && (D == 384 || D == 512 || D == 768 || D == 1280);
+}
+
+// D = 1280, 20 heads: two head groups of 10 per (split, row) in grid.z, 32-key chunks. The E
+// chunk is 32 x 1296 halves = 83 KB (88.6 KB with P and the scores): one block per CU, 4 waves.
+// Each group reads the encoder row (E is read twice per decoder row); one 32-row block would
+// hold Q (2 m-tiles x 20 k-steps), E (20) and C (2 x 20 tiles) in ~400 registers per lane.
+static void xattn_1280(const _Float16* qk, const _Float16* enc, int B, int Te, int H, int nsplit,
+                       float* part_c, float* part_ml, hipStream_t s) {
+  constexpr int D = 1280, CH = 32, HG = 10;
+  const int chunks = (Te + CH - 1) / CH;
+  const int kps = (chunks + nsplit - 1) / nsplit * CH;
+  auto kern = xattn_kernel<D, CH, false, false, false, false, HG>;
+  static_assert(XGeo<D, CH>::LDS <= 160 * 1024, "xattn 1280: LDS per block");
+  static bool attr = false;
+  if (!attr) {
+    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr = true;
+  }
+  kern<<<dim3(nsplit, B, (H + HG - 1) / HG), CH * 8, XGeo<D, CH>::LDS, s>>>(qk, enc, Te, H, kps, part_c, part_ml,
+                                                                            nullptr, nullptr, 0);
+  JANUS_LAUNCH_CHECK();
 }
 
 void xattn_launch(const _Float16* qk, const _Float16* enc, int B, int Te, int D, int H,
                   int nsplit, float* part_c, float* part_ml, _Float16* out, hipStream_t s,
                   bool combine, const int4* pairs, int npairs, bool rev) {
-  JANUS_CHECK(xattn_supported(D, H), "xattn: need D = 64 H in {384, 512, 768}");
+  JANUS_CHECK(xattn_supported(D, H), "xattn: need D = 64 H in {384, 512, 768, 1280}");
   if (B <= 0 || Te <= 0) return;
   JANUS_CHECK(nsplit >= 1 && nsplit <= 63, "xattn: 1..63 key splits");
   JANUS_CHECK(!pairs || (H <= 8 && npairs >= 1 && D <= 512), "xattn: row pairs need H <= 8, D <= 512");
@@ -823,12 +855,13 @@ void xattn_launch(const _Float16* qk, const _Float16* enc, int B, int Te, int D,
   // 64-key chunks (8 waves); D = 768: 32-key chunks
   if (D == 384) xattn_cfg<384, 64>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
   else if (D == 512) xattn_cfg<512, 64>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
-  else xattn_cfg<768, 32>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
+  else if (D == 768) xattn_cfg<768, 32>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
+  else xattn_1280(qk, enc, B, Te, H, nsplit, part_c, part_ml, s);
   if (!combine) return;  // the caller merges (xattn_combine_vproj_launch)
   if (nsplit <= kXCombMax && D <= 512)
     xattn_combine_wide_kernel<<<dim3(H, B), 128, 0, s>>>(part_c, part_ml, nsplit, H, D, out);
   else
-    xattn_combine_kernel<<<B, 256, 0, s>>>(part_c, part_ml, nsplit, H, D, out);
+    xattn_combine_rows(part_c, part_ml, nsplit, B, H, D, out, s);
   JANUS_LAUNCH_CHECK();
 }
 

@@ -59,11 +59,14 @@ struct XGeo {
 // chunk, lane = 16-byte column) straight into their sE rows, and the S phase reads its B
 // fragments back from sE — the fragment-pattern loads touch 16 keys x 64 B per instruction
 // and stream ≈ 20 % slower per CU (tools/stream_probe.hip). One more barrier per chunk.
-template <int D, int CH, bool PAIR, bool DIRECT, bool PF2, bool SC1Q = false, bool ROWLD = false>
+// HG (> 16 heads: the 20-head family at D = 1280): the heads go out in groups of HG <= 16
+// per block — block hz of gridDim.z holds heads [HG hz, HG hz + HG) in its MFMA rows and reads
+// the encoder row itself, so E is read once per head group; 0: every head in one block.
+template <int D, int CH, bool PAIR, bool DIRECT, bool PF2, bool SC1Q = false, bool ROWLD = false, int HG = 0>
 __device__ __forceinline__ void xattn_body(
     const _Float16* __restrict__ qk, const _Float16* __restrict__ enc, int Te, int H, int kps,
     float* __restrict__ part_c, float* __restrict__ part_ml, const int4* __restrict__ pairs,
-    _Float16* __restrict__ out, int s, int nsplit, int by, _Float16* smem, bool rev = false) {
+    _Float16* __restrict__ out, int s, int nsplit, int by, _Float16* smem, bool rev = false, int hz = 0) {
   using G = XGeo<D, CH>;
   constexpr int QP = G::QP, PP = G::PP, KH = G::KH, KS = G::KS, NT = G::NT, NW = G::NW,
                 NKT = G::NKT, HPW = G::HPW;
@@ -72,6 +75,9 @@ __device__ __forceinline__ void xattn_body(
   float* sS = reinterpret_cast<float*>(sP + 16 * PP);  // [2][16][CH] partial scores
   float* sA = sS + 2 * 16 * CH;                // [16] rescale factors
 
+  static_assert(HG == 0 || (HG <= 16 && !PAIR && !DIRECT), "head groups: the one-row split form");
+  const int h0 = HG ? hz * HG : 0;            // first head of this block
+  const int HB = HG ? min(HG, H - h0) : H;    // heads of this block (MFMA rows in use)
   int b = by, b1 = -1, e = by;
   if constexpr (PAIR) {
     const int4 q = pairs[by];
@@ -82,8 +88,8 @@ __device__ __forceinline__ void xattn_body(
   // MFMA row r <-> (decoder row, head): one-row form (b, r) for r < H; PAIR (b, r) for
   // r < 8, (b1, r - 8) above
   auto row_b = [&](int r) { return (PAIR && r >= 8) ? b1 : b; };
-  auto row_h = [&](int r) { return PAIR ? (r & 7) : r; };
-  auto row_ok = [&](int r) { return PAIR ? ((r & 7) < H && (r < 8 || b1 >= 0)) : r < H; };
+  auto row_h = [&](int r) { return PAIR ? (r & 7) : h0 + r; };
+  auto row_ok = [&](int r) { return PAIR ? ((r & 7) < H && (r < 8 || b1 >= 0)) : r < HB; };
   const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
   const int t0 = s * kps, t1 = min(Te, t0 + kps);
   const _Float16* eb = enc + (int64_t)e * Te * D;
@@ -189,7 +195,7 @@ __device__ __forceinline__ void xattn_body(
       if constexpr (PAIR) {
         if (!row_ok(h)) continue;  // wave-uniform
       } else {
-        if (h >= H) break;  // wave-uniform
+        if (h >= HB) break;  // wave-uniform
       }
       const bool valid = lane < nk;
       const float sc = valid ? sS[h * CH + lane] + sS[(16 + h) * CH + lane] : -INFINITY;

@@ -196,7 +196,7 @@ def stagger_plan(sets, pos, started, k, S, fresh):
 
 class _Batch:
     """One serving batch in flight: its clips' seek-loop states, whole-clip features (fp16
-    [B][F][80] on the GPU, kept until the last window of the batch has entered the decoder)
+    [B][F][n_mels] on the GPU, kept until the last window of the batch has entered the decoder)
     and prosody, until every clip's last window has settled."""
 
     def __init__(self, B, feats, contents, mode, override, timestamp, max_length):
@@ -332,9 +332,9 @@ class JanusPipeline(PacketRenderer):
     # ------------------------------------------------------------------ features
     def _features(self, pcm, offsets, lengths):
         """Whole-clip log-mel of every clip's [::3] (faster-whisper's one FeatureExtractor
-        call per transcribe, normalised over all of the clip's frames), fp16 [B][F][80] with
+        call per transcribe, normalised over all of the clip's frames), fp16 [B][F][n_mels] with
         F = max(3000, the longest clip's content frames), zeros past each clip's content; and
-        the first windows' mel [B][3000][80] (a view when F = 3000)."""
+        the first windows' mel [B][3000][n_mels] (a view when F = 3000)."""
         B = len(lengths)
         cont = contents_of(lengths)
         F = max(N_FRAMES, max(cont) if cont else 0)

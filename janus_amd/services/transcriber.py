@@ -59,7 +59,8 @@ import torch
 from .. import _native as nat
 from ..common import wavio
 from ..tokenizer import LANGUAGES, SOT_PREV, TASKS
-from ..whisper import CONFIGS, WhisperEngine, check_beam_args, shared_rows_in_place
+from ..whisper import (CONFIGS, WhisperEngine, check_beam_args, check_encoder_compute,
+                       check_family_features, resolve_model, shared_rows_in_place)
 from . import vad_filter as vf
 
 WINDOW_16K = 480000
@@ -472,9 +473,10 @@ class _Stream:
         far. all_language_probs are those of the last window examined."""
         probs = np.asarray(probs, np.float64)
         i = int(np.argmax(probs))
-        self.language_votes.append((LANGUAGES[i], float(probs[i])))
+        codes = getattr(tk, "languages", LANGUAGES)   # 99, or the large-v3 layout's 100
+        self.language_votes.append((codes[i], float(probs[i])))
         order = np.argsort(-probs, kind="stable")
-        self.all_language_probs = [(LANGUAGES[int(k)], float(probs[int(k)])) for k in order]
+        self.all_language_probs = [(codes[int(k)], float(probs[int(k)])) for k in order]
         if probs[i] > threshold:
             self.language, self.language_probability = self.language_votes[-1]
             self.language_pending = False
@@ -608,15 +610,16 @@ def advance(tk, s, size, c0, r, nd, sampled: int = 0, word_timestamps: bool = Fa
         s.prompt_reset_since = len(s.all_tokens)
 
 
-def gather_windows(items, n_frames: int = N_FRAMES, device=None):
-    """fp16 [len(items)][n_frames][80]: item j = (features [B][F][80] fp16 device tensor, row,
-    seek, size) -> features[row, seek:seek + size] followed by zeros (faster-whisper's
+def gather_windows(items, n_frames: int = N_FRAMES, device=None, n_mels: int = 80):
+    """fp16 [len(items)][n_frames][n_mels]: item j = (features [B][F][n_mels] fp16 device tensor,
+    row, seek, size) -> features[row, seek:seek + size] followed by zeros (faster-whisper's
     ``features[:, seek:seek + segment_size]`` + pad_or_trim). One index gather per distinct
-    features tensor (a serving batch's windows come out of one [B][F][80] tensor)."""
+    features tensor (a serving batch's windows come out of one [B][F][n_mels] tensor). The bin
+    count is the features' own; ``n_mels`` (the model's cfg.n_mels) only shapes an empty result."""
     if not items:
-        return torch.zeros(0, n_frames, 80, dtype=torch.float16, device=device)
+        return torch.zeros(0, n_frames, n_mels, dtype=torch.float16, device=device)
     dev = items[0][0].device
-    out = torch.zeros(len(items), n_frames, 80, dtype=torch.float16, device=dev)
+    out = torch.zeros(len(items), n_frames, items[0][0].shape[-1], dtype=torch.float16, device=dev)
     t = torch.arange(n_frames, device=dev)
     groups = {}
     for j, (f, row, seek, size) in enumerate(items):
@@ -637,7 +640,7 @@ def gather_windows(items, n_frames: int = N_FRAMES, device=None):
         rows, seeks, sizes, js = idx[:, 0], idx[:, 1], idx[:, 2], idx[:, 3]
         src = seeks[:, None] + t[None, :]
         valid = (t[None, :] < sizes[:, None]) & (src < F)
-        g = f[rows[:, None], torch.where(valid, src, 0)]          # [n][n_frames][80]
+        g = f[rows[:, None], torch.where(valid, src, 0)]          # [n][n_frames][n_mels]
         out[js] = torch.where(valid[..., None], g, torch.zeros((), dtype=g.dtype, device=dev))
     return out
 
@@ -687,6 +690,7 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     (the default), no VAD call is made and nothing differs.
     Returns one _Stream (segments + gate counters) per utterance."""
     check_beam_args(beam_size, length_penalty)
+    check_family_features(getattr(engine, "cfg", None), beam_size, word_timestamps)
     if beam_size > 1 and speculative:
         raise NotImplementedError("speculative=True decodes greedily in one call; beam_size > 1 "
                                   "needs speculative=False")
@@ -828,13 +832,13 @@ class WhisperModel:
 
     def __init__(self, model_size: str, device: str = "auto", compute_type: str = "default",
                  *, apply_compute_type: bool = False, vad_weights: dict = None, **_ignored):
-        if model_size not in CONFIGS:
-            raise ValueError(f"unknown model size {model_size!r}; one of {sorted(CONFIGS)}")
+        model_size = resolve_model(model_size)   # ValueError: unknown; "turbo" -> "large-v3-turbo"
         if device not in DEVICES:
             raise ValueError(f"unsupported device {device!r}; one of {DEVICES}")
         self.effective_compute_type, enc_compute = resolve_compute_type(compute_type, apply_compute_type)
         self.model_size = model_size
         self.requested_device, self.requested_compute_type = device, compute_type
+        check_encoder_compute(CONFIGS[model_size], enc_compute)   # NotImplementedError: int8 at 1280
         self.engine = WhisperEngine(CONFIGS[model_size], encoder_compute=enc_compute)
         self.stats = {"windows": 0, "needs_fallback": 0, "no_speech_skips": 0, "fallback_decodes": 0}
         # vad_filter: silero weights (default: JANUS_VAD_DIR; none: the energy stand-in); the
@@ -857,8 +861,10 @@ class WhisperModel:
 
     @property
     def supported_languages(self):
-        """faster-whisper's supported_languages: the 99 codes, or ["en"] for a ``*.en`` model."""
-        return list(LANGUAGES) if self.is_multilingual else ["en"]
+        """faster-whisper's supported_languages: the 99 codes (100 on the large-v3 family), or
+        ["en"] for a ``*.en`` model."""
+        tk = self.engine.tokenizer
+        return list(getattr(tk, "languages", LANGUAGES)) if self.is_multilingual else ["en"]
 
     def _check_language(self, language, task):
         """``*.en``: English transcription only (NotImplementedError, as before the
@@ -920,6 +926,7 @@ class WhisperModel:
         finds is decoded and every time is restored onto ``audio`` (generate_segments);
         ``info.duration_after_vad`` is the audio kept, ``info.vad_options`` the options."""
         check_beam_args(beam_size, length_penalty, patience)
+        check_family_features(getattr(self.engine, "cfg", None), beam_size, word_timestamps)
         if hallucination_silence_threshold is not None:
             raise NotImplementedError("hallucination_silence_threshold is not supported")
         self._check_language(language, task)

@@ -11,6 +11,11 @@ language tokens 50259..50357, <|translate|> 50358, <|transcribe|> 50359, <|start
 <|startofprev|> 50361, <|nospeech|> 50362, <|notimestamps|> 50363, timestamps from 50364; its
 start sequence is [sot, <|language|>, <|task|>].
 
+The large-v3 vocabulary (large-v3 / large-v3-turbo / distil-large-v3; 51 866 ids) has one more
+language, <|yue|>, appended to the 99: <|startoftranscript|> 50258, the 100 language tokens
+50259..50358, <|translate|> 50359, <|transcribe|> 50360, <|startoflm|> 50361, <|startofprev|>
+50362, <|nospeech|> 50363, <|notimestamps|> 50364, timestamps from 50365.
+
 No tokenizer files exist offline. If ``JANUS_WHISPER_DIR`` holds a Hugging Face
 ``tokenizer.json``, it is used through the ``tokenizers`` package; otherwise a
 deterministic synthetic vocabulary of the same size is used: ids 0..255 are the 256
@@ -36,6 +41,7 @@ NO_TIMESTAMPS = 50362
 TIMESTAMP_BEGIN = 50363
 N_VOCAB_EN = 51864
 N_VOCAB_MULTILINGUAL = 51865
+N_VOCAB_V3 = 51866
 BLANK = 220
 
 # the 99 language tokens in openai/whisper's order (tokenizer.LANGUAGES)
@@ -43,6 +49,8 @@ LANGUAGES = ("en zh de es ru ko fr ja pt tr pl ca nl ar sv it id hi fi vi he uk 
              "ta no th ur hr bg lt la mi ml cy sk te fa lv bn sr az sl kn et mk br eu is hy ne mn bs "
              "kk sq sw gl mr pa si km sn yo so af oc ka be tg sd gu am yi lo uz fo ht ps tk nn mt sa "
              "lb my bo tl mg as tt haw ln ha ba jw su").split()
+# the large-v3 family's 100: the same order with Cantonese appended
+LANGUAGES_V3 = LANGUAGES + ["yue"]
 TASKS = ("transcribe", "translate")
 # languages written without spaces: words are the unicode pieces (faster-whisper's
 # Tokenizer.split_to_word_tokens)
@@ -65,21 +73,29 @@ def bytes_to_unicode_order():
 class WhisperTokenizer:
     """One token space: ``multilingual=False`` the ``*.en`` ids (the module constants),
     ``multilingual=True`` the 51 865-entry vocabulary with every special id one higher and
-    the start sequence [sot, <|language|>, <|task|>]."""
+    the start sequence [sot, <|language|>, <|task|>]. ``n_vocab`` (None: from
+    ``multilingual``) names the layout outright: 51 864, 51 865 or 51 866 — the large-v3
+    layout, multilingual with 100 languages, so every id past them one higher again."""
 
     def __init__(self, path: str = None, seed: int = 1234, multilingual: bool = False,
-                 language: str = "en", task: str = "transcribe"):
-        self.multilingual = bool(multilingual)
+                 language: str = "en", task: str = "transcribe", n_vocab: int = None):
+        if n_vocab is None:
+            n_vocab = N_VOCAB_MULTILINGUAL if multilingual else N_VOCAB_EN
+        if n_vocab not in (N_VOCAB_EN, N_VOCAB_MULTILINGUAL, N_VOCAB_V3):
+            raise ValueError(f"no token layout for a vocabulary of {n_vocab}")
+        self.multilingual = n_vocab != N_VOCAB_EN
+        self.languages = LANGUAGES_V3 if n_vocab == N_VOCAB_V3 else LANGUAGES
         up = 1 if self.multilingual else 0
+        up2 = up + (1 if n_vocab == N_VOCAB_V3 else 0)   # ids past the language tokens
         self.eot, self.sot = EOT + up, SOT + up
-        self.translate, self.transcribe = TRANSLATE + up, TRANSCRIBE + up
-        self.sot_lm, self.sot_prev = SOT_LM + up, SOT_PREV + up
-        self.no_speech = NO_SPEECH + up
-        self.no_timestamps = NO_TIMESTAMPS + up
-        self.timestamp_begin = TIMESTAMP_BEGIN + up
+        self.translate, self.transcribe = TRANSLATE + up2, TRANSCRIBE + up2
+        self.sot_lm, self.sot_prev = SOT_LM + up2, SOT_PREV + up2
+        self.no_speech = NO_SPEECH + up2
+        self.no_timestamps = NO_TIMESTAMPS + up2
+        self.timestamp_begin = TIMESTAMP_BEGIN + up2
         self.language_begin = self.sot + 1
-        self.n_languages = len(LANGUAGES)
-        self.n_vocab = N_VOCAB_MULTILINGUAL if self.multilingual else N_VOCAB_EN
+        self.n_languages = len(self.languages)
+        self.n_vocab = n_vocab
         self.blank = BLANK
         self.language, self.task = language, task
         # *.en: no language / task tokens
@@ -89,9 +105,13 @@ class WhisperTokenizer:
             from tokenizers import Tokenizer
             self._hf = Tokenizer.from_file(os.path.join(path, "tokenizer.json"))
             # the decoder's prompt and rules use this layout's special-token ids: the file must agree
-            layout = "multilingual" if self.multilingual else "*.en"
-            for name, want in (("<|endoftext|>", self.eot), ("<|startoftranscript|>", self.sot),
-                               ("<|startofprev|>", self.sot_prev), ("<|notimestamps|>", self.no_timestamps)):
+            layout = ("large-v3" if n_vocab == N_VOCAB_V3 else "multilingual") if self.multilingual else "*.en"
+            names = [("<|endoftext|>", self.eot), ("<|startoftranscript|>", self.sot),
+                     ("<|startofprev|>", self.sot_prev), ("<|notimestamps|>", self.no_timestamps)]
+            if n_vocab == N_VOCAB_V3:   # the ids the 100th language moved
+                names += [("<|yue|>", self.language_begin + 99), ("<|translate|>", self.translate),
+                          ("<|transcribe|>", self.transcribe), ("<|nospeech|>", self.no_speech)]
+            for name, want in names:
                 got = self._hf.token_to_id(name)
                 if got != want:
                     raise ValueError(f"tokenizer.json: {name} is {got}, expected {want} ({layout} layout)")
@@ -103,16 +123,20 @@ class WhisperTokenizer:
 
     # ---- language / task tokens
     def language_token(self, code: str) -> int:
-        """<|code|>'s id; ValueError for a code that is none of the 99."""
-        if not isinstance(code, str) or code not in LANGUAGES:
+        """<|code|>'s id; ValueError for a code that is none of this layout's languages."""
+        if not isinstance(code, str) or code not in self.languages:
             raise ValueError(f"unknown language code {code!r}")
-        return self.language_begin + LANGUAGES.index(code)
+        return self.language_begin + self.languages.index(code)
+
+    def supported_languages(self):
+        """The codes this layout has tokens for: 99, 100 (large-v3), or ["en"] for ``*.en``."""
+        return list(self.languages) if self.multilingual else ["en"]
 
     def language_code(self, token: int) -> str:
         i = int(token) - self.language_begin
         if not 0 <= i < self.n_languages:
             raise ValueError(f"token {token} is no language token")
-        return LANGUAGES[i]
+        return self.languages[i]
 
     def task_token(self, task: str) -> int:
         if task not in TASKS:
@@ -292,6 +316,18 @@ class WhisperTokenizer:
         return " ".join(texts).strip()
 
 
-def load_tokenizer(multilingual: bool = False):
-    return WhisperTokenizer(os.environ.get("JANUS_WHISPER_DIR"), multilingual=multilingual)
+def layout_vocab(n_vocab: int) -> int:
+    """The token layout a model of ``n_vocab`` entries decodes with: the large-v3 layout for
+    exactly 51 866, the multilingual one from 51 865 on, else ``*.en`` (test models with a
+    cut vocabulary keep the ``*.en`` ids, as WhisperConfig.multilingual says)."""
+    if n_vocab == N_VOCAB_V3:
+        return N_VOCAB_V3
+    return N_VOCAB_MULTILINGUAL if n_vocab >= N_VOCAB_MULTILINGUAL else N_VOCAB_EN
+
+
+def load_tokenizer(multilingual: bool = False, n_vocab: int = None):
+    """The tokenizer of a model: ``n_vocab`` (WhisperConfig.n_vocab) picks the layout."""
+    if n_vocab is not None:
+        n_vocab = layout_vocab(n_vocab)
+    return WhisperTokenizer(os.environ.get("JANUS_WHISPER_DIR"), multilingual=multilingual, n_vocab=n_vocab)
 

@@ -38,7 +38,8 @@ class WhisperConfig:
 
     @property
     def multilingual(self) -> bool:
-        """The 51 865-entry vocabulary: language and task tokens, every special id one higher."""
+        """The 51 865- or 51 866-entry vocabulary: language and task tokens (tokenizer.py picks
+        the layout from n_vocab)."""
         return self.n_vocab >= tok.N_VOCAB_MULTILINGUAL
 
 
@@ -52,7 +53,48 @@ CONFIGS = {
     "tiny": WhisperConfig("tiny", 384, 6, 4, 4, n_vocab=tok.N_VOCAB_MULTILINGUAL),
     "base": WhisperConfig("base", 512, 8, 6, 6, n_vocab=tok.N_VOCAB_MULTILINGUAL),
     "small": WhisperConfig("small", 768, 12, 12, 12, n_vocab=tok.N_VOCAB_MULTILINGUAL),
+    # the large-v3 family: d_model 1280, 20 heads, 128 mel bins, the 100-language vocabulary;
+    # turbo and distil keep large-v3's encoder over a 4- / 2-layer decoder
+    "large-v3": WhisperConfig("large-v3", 1280, 20, 32, 32, n_mels=128, n_vocab=tok.N_VOCAB_V3),
+    "large-v3-turbo": WhisperConfig("large-v3-turbo", 1280, 20, 32, 4, n_mels=128, n_vocab=tok.N_VOCAB_V3),
+    "distil-large-v3": WhisperConfig("distil-large-v3", 1280, 20, 32, 2, n_mels=128, n_vocab=tok.N_VOCAB_V3),
 }
+MODEL_ALIASES = {"turbo": "large-v3-turbo"}   # faster-whisper's short name
+
+
+def resolve_model(name: str) -> str:
+    """A model name or alias -> its CONFIGS key; ValueError for an unknown one."""
+    name = MODEL_ALIASES.get(name, name)
+    if name not in CONFIGS:
+        raise ValueError(f"unknown model size {name!r}; one of {sorted(CONFIGS) + sorted(MODEL_ALIASES)}")
+    return name
+
+
+def large_family(cfg) -> bool:
+    """The 1280-wide, 20-head models."""
+    return cfg is not None and getattr(cfg, "d_model", 0) > 768
+
+
+def check_family_features(cfg, beam_size: int = 1, word_timestamps: bool = False) -> None:
+    """What the large-v3 family does not run in this build (second tier):
+    beam search (no beam partials of the vocabulary projection at K = 1280) and word
+    timestamps. NotImplementedError naming the feature, before any GPU work."""
+    if not large_family(cfg):
+        return
+    if beam_size > 1:
+        raise NotImplementedError(f"beam_size {beam_size} on {cfg.name}: the 1280-wide models decode "
+                                  "greedily or sampled (beam_size 1) in this build")
+    if word_timestamps:
+        raise NotImplementedError(f"word_timestamps on {cfg.name}: the alignment pass is not built for "
+                                  "the 1280-wide, 20-head models")
+
+
+def check_encoder_compute(cfg, mode) -> None:
+    """int8 encoder projections stop at K = 3072 (quant_rows_i8); fc2 of a 1280-wide model
+    has K = 5120: NotImplementedError there."""
+    if mode in ("int8", ENCODER_COMPUTE["int8"]) and large_family(cfg):
+        raise NotImplementedError(f"int8 encoder compute on {cfg.name}: fc2's K = {cfg.ffn} exceeds the "
+                                  "int8 path's 3072; these models run float16")
 
 
 class janus_whisper_config(ctypes.Structure):
@@ -148,11 +190,14 @@ def mel_filters(sr=16000, n_fft=400, n_mels=80, fmin=0.0, fmax=8000.0) -> np.nda
         w[i] = np.maximum(0, np.minimum(lower, upper))
     enorm = 2.0 / (f_pts[2:n_mels + 2] - f_pts[:n_mels])
     w *= enorm[:, None]
-    return w.T.astype(np.float32)  # [201][80]
+    return w.T.astype(np.float32)  # [201][n_mels]
 
 
-def mel_constants():
-    """("mel.basis" [400][416], "mel.filters" [208][80]) for janus_whisper_set_tensor."""
+def mel_constants(n_mels: int = 80):
+    """("mel.basis" [400][416], "mel.filters" [208][n_mels]) for janus_whisper_set_tensor;
+    n_mels 80 or 128."""
+    if n_mels not in (80, 128):
+        raise ValueError(f"mel_constants: 80 or 128 bins, not {n_mels}")
     n = np.arange(400)
     hann = 0.5 - 0.5 * np.cos(2 * np.pi * n / 400)  # periodic (torch.hann_window / np.hanning(401)[:-1])
     k = np.arange(201)
@@ -160,8 +205,8 @@ def mel_constants():
     basis = np.zeros((400, 416))
     basis[:, :201] = hann[:, None] * np.cos(ang)
     basis[:, 208:208 + 201] = hann[:, None] * np.sin(ang)
-    filt = np.zeros((208, 80), np.float32)
-    filt[:201] = mel_filters()
+    filt = np.zeros((208, n_mels), np.float32)
+    filt[:201] = mel_filters(n_mels=n_mels)
     return basis.astype(np.float32), filt
 
 
@@ -252,6 +297,12 @@ def load_weights(cfg: WhisperConfig, seed: int = 0) -> dict:
         if emb is None or emb.shape != (cfg.n_vocab, cfg.d_model):
             raise ValueError(f"checkpoint does not match {cfg.name}: decoder.embed_tokens.weight "
                              f"{None if emb is None else emb.shape}")
+        # the stem decides the feature size: 80 or 128 mel bins (large-v3 family)
+        conv1 = W.get("encoder.conv1.weight")
+        if conv1 is None or tuple(conv1.shape) != (cfg.d_model, cfg.n_mels, 3):
+            raise ValueError(f"checkpoint does not match {cfg.name}: encoder.conv1.weight "
+                             f"{None if conv1 is None else tuple(conv1.shape)}, the config has "
+                             f"{(cfg.d_model, cfg.n_mels, 3)}")
         # depth per side: a distil checkpoint keeps the teacher's encoder (12 layers at
         # small.en's width) over a 4-layer decoder, so the two counts are checked apart
         for side, want in (("encoder", cfg.enc_layers), ("decoder", cfg.dec_layers)):
@@ -351,18 +402,19 @@ class WhisperEngine:
     def __init__(self, cfg: WhisperConfig, weights: dict = None, seed: int = 0,
                  encoder_compute: str = "float16", alignment_heads=None):
         mode = encoder_compute_mode(encoder_compute)
+        check_encoder_compute(cfg, mode)
         if alignment_heads is not None:
             alignment_heads = check_alignment_heads(cfg, alignment_heads)
         self.device = nat.require_gpu()
         self.cfg = cfg
-        self.tokenizer = tok.load_tokenizer(multilingual=cfg.multilingual)
+        self.tokenizer = tok.load_tokenizer(multilingual=cfg.multilingual, n_vocab=cfg.n_vocab)
         c = janus_whisper_config(cfg.n_mels, cfg.n_audio_ctx, cfg.d_model, cfg.n_heads,
                                  cfg.enc_layers, cfg.dec_layers, cfg.n_vocab, cfg.n_text_ctx)
         h = ctypes.c_void_p()
         nat.call("janus_whisper_create", ctypes.addressof(c), ctypes.addressof(h))
         self._h = h
         weights = weights if weights is not None else load_weights(cfg, seed)
-        basis, filt = mel_constants()
+        basis, filt = mel_constants(cfg.n_mels)
         weights = dict(weights)
         weights["mel.basis"] = basis
         weights["mel.filters"] = filt
@@ -386,6 +438,7 @@ class WhisperEngine:
     def set_encoder_compute(self, mode: str) -> None:
         """Switch the encoder's linear layers between "float16" and "int8" (either direction,
         between calls); the int8 weights are quantised on the first int8 encode()."""
+        check_encoder_compute(self.cfg, mode)
         nat.call("janus_whisper_set_encoder_compute", self._h, encoder_compute_mode(mode))
 
     def set_tensor(self, name: str, arr) -> None:
@@ -406,17 +459,18 @@ class WhisperEngine:
     def logmel(self, pcm: torch.Tensor, offsets: torch.Tensor, batch: int, decim: int,
                want_raw: bool = False):
         frames = 2 * self.cfg.n_audio_ctx
-        mel = torch.empty(batch, frames, 80, dtype=torch.float16, device=self.device)
-        raw = torch.empty(batch, frames, 80, dtype=torch.float32, device=self.device) if want_raw else None
+        nm = self.cfg.n_mels
+        mel = torch.empty(batch, frames, nm, dtype=torch.float16, device=self.device)
+        raw = torch.empty(batch, frames, nm, dtype=torch.float32, device=self.device) if want_raw else None
         nat.call("janus_whisper_logmel", self._h, pcm.data_ptr(), offsets.data_ptr(), batch, decim,
                  raw.data_ptr() if raw is not None else None, mel.data_ptr(), nat.stream_ptr())
         return (mel, raw) if want_raw else mel
 
     def logmel_frames(self, pcm: torch.Tensor, offsets: torch.Tensor, batch: int, decim: int,
                       frames: int) -> torch.Tensor:
-        """Whole-clip features (janus_whisper_logmel_frames): fp16 [batch][frames][80],
+        """Whole-clip features (janus_whisper_logmel_frames): fp16 [batch][frames][n_mels],
         normalised over every frame of each clip, 0.0 from each clip's content end on."""
-        mel = torch.empty(batch, frames, 80, dtype=torch.float16, device=self.device)
+        mel = torch.empty(batch, frames, self.cfg.n_mels, dtype=torch.float16, device=self.device)
         nat.call("janus_whisper_logmel_frames", self._h, pcm.data_ptr(), offsets.data_ptr(), batch,
                  decim, frames, mel.data_ptr(), nat.stream_ptr())
         return mel
@@ -585,6 +639,7 @@ class WhisperEngine:
         windows x beam_size <= 512; staggered rows (``pos_offset``) and ``temperature`` > 0
         are rejected, a ``persistent`` request runs the launch path (decode_path())."""
         check_beam_args(beam_size, length_penalty)
+        check_family_features(getattr(self, "cfg", None), beam_size)   # (beam_size 1 there: the C entry refuses)
         if pos_offset is not None:
             raise ValueError("decode_beam: staggered rows (pos_offset) are not supported")
         if not np.isscalar(temperature) or temperature > 0:
@@ -703,7 +758,8 @@ class WhisperEngine:
     def detect_language(self, enc: torch.Tensor):
         """janus_whisper_detect_language over ``enc`` [B][1500][d]: (probs f32 [B][n_languages]
         — the softmax over the language tokens alone of one <|startoftranscript|> position —,
-        best int32 [B], indices into tokenizer LANGUAGES), device tensors (include/janus.h,
+        best int32 [B], indices into the tokenizer's ``languages``: 99, or 100 on the large-v3
+        family), device tensors (include/janus.h,
         DESIGN.md §5m). ValueError on an English-only engine."""
         t = self.tokenizer
         if not self.cfg.multilingual:
@@ -729,6 +785,7 @@ class WhisperEngine:
         matrix A the path was solved on; ``phases``: janus_whisper_align's measurement mask;
         ``sot_sequences``: one start sequence per window instead of the tokenizer's (a
         multilingual model's per-utterance language and task)."""
+        check_family_features(getattr(self, "cfg", None), word_timestamps=True)
         t = self.tokenizer
         if len(texts) != len(sizes) or (enc_index is not None and len(enc_index) != len(texts)):
             raise ValueError("align: one text, one size (and one enc_index) per window")
@@ -836,7 +893,7 @@ def shared_rows_in_place(cfg) -> bool:
     sampled batches small (services/transcriber.py FALLBACK_ROWS_GATHER)."""
     if cfg is None:
         return True
-    return cfg.n_heads <= 8 and cfg.d_model <= 512
+    return cfg.n_heads <= 8 and cfg.d_model <= 512   # (20 heads / 1280: gathered too)
 
 
 @dataclasses.dataclass
