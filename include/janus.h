@@ -325,6 +325,29 @@ typedef struct {
   int lanes;               /* concurrent decoder lanes of janus_whisper_decode_greedy: the
                               batch split over streams and host threads (0 = 1; slower at
                               B = 64) */
+  /* History rules: repetition_penalty p (> 0; 0 and 1 = off, so zeroed fields are a call
+   * without them) and no_repeat_ngram_size n (>= 0; 0 = off), faster-whisper's options of the
+   * same names. CTranslate2 cannot be run offline, so this rule is PARITY UNPINNED (as the beam
+   * search and alignment rules); what is built, per row, with g the tokens the row has SAMPLED
+   * in this call (timestamps included; the prompt — <|startofprev|> text, hotwords, the sot
+   * sequence — is not part of g) and m = len(g):
+   *  1. Penalty: for every distinct token t of g, logit[t] = logit[t] * p if logit[t] < 0,
+   *     else logit[t] / p. Once per distinct token, in fp32, before every other rule.
+   *  2. No-repeat n-grams: the tokens { g[i+n-1] : 0 <= i <= m-n and g[i .. i+n-2] ==
+   *     g[m-n+1 .. m-1] } are banned, i.e. treated exactly like the suppress list (-inf).
+   *     n = 1 bans every token of g; nothing is banned while m < n; overlapping matches count.
+   *  3. Everything after runs unchanged on the penalised, banned logits: SuppressBlank, the
+   *     timestamp rules, the timestamp-mass rule, the filtered log-sum-exp, the argmax (or
+   *     Gumbel-max with key = penalised logit * 1/T + noise) and the accumulated
+   *     log-probability (untempered, penalised, filtered).
+   *  4. The raw statistics behind no_speech_prob stay unpenalised.
+   * Honoured by janus_whisper_decode_greedy_ex, _sample_ex and _sample_rows_ex, shared
+   * encoder rows (enc_index) included, for one more small launch per position; REJECTED
+   * (non-zero status, janus_last_error, nothing enqueued) with beam search, with staggered
+   * rows (pos_offset), for p < 0 and for n < 0. A `persistent` request with history rules
+   * runs the launch path (janus_whisper_decode_path reports 0). */
+  float repetition_penalty;
+  int no_repeat_ngram_size;
 } janus_decode_options;
 
 /* janus_decode_options.path_flags */

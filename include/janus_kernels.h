@@ -231,6 +231,31 @@ int janus_logits_partial_f16(const uint16_t* A, const uint16_t* W, int K, int V,
                              const uint8_t* smask, const int32_t* row_rules, int max_blocks,
                              float inv_temp, const uint32_t* seeds, int pos, void* parts,
                              void* stream);
+/*
+ * History rules (janus_decode_options.repetition_penalty / no_repeat_ngram_size), the two kernels
+ * alone. The history words: uint32 [groups][(V + 15) / 16 tiles][rg rows], rg = 64 rows per
+ * group up to K = 768 and 32 at K = 1280, row b in group b / rg; bits 0-15 of a word are the
+ * tile's penalised columns, bits 16-31 its banned ones. janus_history_words returns their
+ * count for batch rows (a count, not a status).
+ *
+ * janus_history_rules: positions pos0 .. pos0 + n_pos - 1 of every row in turn, one launch
+ * each, as a decode call's positions run it: tokens [batch][ld] int32 (given rows, nothing is
+ * sampled), plen [batch] the rows' prompt lengths, n = no_repeat_ngram_size, hist the words
+ * (the caller zeroes them before a row's first position).
+ *
+ * janus_logits_partial_hist_f16: janus_logits_partial_f16 with the history words applied in
+ * the epilogue (hist as above for this K, repetition_penalty > 0): the penalised, banned
+ * logits go through the filter, t_v / m_raw / s_raw stay on the raw ones.
+ */
+int janus_history_words(int V, int K, int batch);
+int janus_history_rules(const int32_t* tokens, int ld, int batch, const int32_t* plen, int n, int V,
+                        int K, int pos0, int n_pos, uint32_t* hist, void* stream);
+int janus_logits_partial_hist_f16(const uint16_t* A, const uint16_t* W, int K, int V, int batch,
+                                  int eot, int suppress_blank, int blank, int ts_begin,
+                                  int no_timestamps, int max_initial_ts, int target,
+                                  const uint8_t* smask, const int32_t* row_rules, int max_blocks,
+                                  float inv_temp, const uint32_t* seeds, int pos, void* parts,
+                                  const uint32_t* hist, float repetition_penalty, void* stream);
 int janus_beam_logits_topk_f16(const uint16_t* A, const uint16_t* W, int K, int V, int batch,
                                int eot, int suppress_blank, int blank, int ts_begin,
                                int no_timestamps, int max_initial_ts, const uint8_t* smask,

@@ -130,6 +130,11 @@ SIGNATURES = {
                                    _I32, _P, _P, _I32, _P, _P, _P, _P, _P],
     "janus_logits_partial_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P,
                                  _I32, _F32, _P, _I32, _P, _P],
+    # history rules (repetition penalty / no-repeat n-grams): the bit-set kernel, the HIST projection
+    "janus_history_words": [_I32, _I32, _I32],
+    "janus_history_rules": [_P, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P, _P],
+    "janus_logits_partial_hist_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P,
+                                      _I32, _F32, _P, _I32, _P, _P, _F32, _P],
     "janus_beam_step": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P,
                         _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "janus_beam_reorder_f16": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],

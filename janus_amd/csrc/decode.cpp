@@ -96,6 +96,7 @@ struct LaneBuffers {
   BeamTop* btop;
   int32_t *bint, *bfin;
   float* bfs;
+  uint32_t* hist;                // null: no history rules
 
   void append_key(std::vector<int64_t>& key) const {
     static_assert(std::is_trivially_copyable<LaneBuffers>::value && sizeof(LaneBuffers) % sizeof(int64_t) == 0 &&
@@ -152,6 +153,7 @@ static LaneBuffers ensure_buffers(janus_whisper* w, DecLane& Z, const DecodePlan
   Z.d_roff.ensure(sizeof(int32_t) * B);
   Z.d_seed.ensure(sizeof(uint32_t) * B);
   if (P.row_temps) Z.d_itemp.ensure(sizeof(float) * B);
+  if (P.hist()) Z.d_hist.ensure(sizeof(uint32_t) * history_words(V, d, B));
   if (P.xabs) {
     Z.d_xqk.ensure(sizeof(_Float16) * B * H * d);
     Z.d_xc.ensure(sizeof(_Float16) * B * H * d);
@@ -199,6 +201,7 @@ static LaneBuffers ensure_buffers(janus_whisper* w, DecLane& Z, const DecodePlan
   b.segbar = Z.d_segbar.as<unsigned>(); b.segerr = Z.d_segerr.as<unsigned>();
   b.btop = Z.d_btop.as<BeamTop>(); b.bint = Z.d_bint.as<int32_t>(); b.bfin = Z.d_bfin.as<int32_t>();
   b.bfs = Z.d_bfs.as<float>();
+  b.hist = P.hist() ? Z.d_hist.as<uint32_t>() : nullptr;
   return b;
 }
 
@@ -259,6 +262,9 @@ static void upload_inputs(janus_whisper* w, DecLane& Z, const DecodePlan& P, con
     rules_init_launch(Z.d_rules.as<RowRules>() + f0, f1 - f0, s);
   }
   if (P.beam_k) beam_init_launch(bst, P.nwin, s);
+  // history rules: every call starts from empty bit sets (enqueued in front of the positions,
+  // so a replayed graph never sees the previous call's bits)
+  if (b.hist) JANUS_HIP(hipMemsetAsync(b.hist, 0, sizeof(uint32_t) * history_words(V, w->cfg.d_model, B), s));
   JANUS_HIP(hipMemsetAsync(Z.d_lncnt.p, 0, sizeof(int) * 64, s));
 }
 
@@ -508,12 +514,14 @@ struct DecodeStep : LaneBuffers {
   void tail(int pos) const {
     const int nblk = P.nblk, nwin = P.nwin;
     if (!ln_fuse && !lnp_fin && !layerk) layernorm_launch(x, fin_g, fin_b, a, B, d, 1e-5f, s);
+    // history rules: the token at pos into the rows' bit sets, one launch more per position
+    if (hist) history_rules_launch(tokens, maxlen, pos, prompt, P.ngram, V, logits_row_group(d), hist, B, s);
     logits_partial_launch(a, d, w->tok16.as<_Float16>(), d, V, B, R, smask,
                           rules, parts, s,
                           lnp_fin ? x : nullptr, d, fin_g, fin_b, P.lg_cap,
                           P.sampling ? seed : nullptr, pos,
                           P.row_temps ? itemp : nullptr,
-                          P.beam_k ? btop : nullptr);
+                          P.beam_k ? btop : nullptr, hist, P.rep_pen);
     if (P.beam_k) {
       beam_step_launch(parts, btop, nblk, R, rules,
                        tokens, maxlen, pos, done, sum_lp, n_tokens, prompt,

@@ -142,6 +142,19 @@ static void plan_rows(DecodePlan& P, const janus_whisper_config& c, const janus_
     P.beam_k = beam->k;
     P.nwin = B / beam->k;
   }
+  // history rules (janus_decode_options, rule at include/janus.h): a penalty of 0 or 1 and n = 0 are off
+  {
+    const float p = opt.repetition_penalty;
+    const int n = opt.no_repeat_ngram_size;
+    JANUS_CHECK(p >= 0.f, "decode: repetition_penalty must be > 0 (0 or 1: off)");   // (NaN fails too)
+    JANUS_CHECK(n >= 0, "decode: no_repeat_ngram_size must be >= 0");
+    P.rep_pen = p == 0.f ? 1.f : p;
+    P.ngram = n;
+    if (P.hist()) {
+      JANUS_CHECK(!beam, "decode: beam search takes no repetition_penalty / no_repeat_ngram_size");
+      JANUS_CHECK(!stagger, "decode: staggered rows (pos_offset) take no repetition_penalty / no_repeat_ngram_size");
+    }
+  }
   JANUS_CHECK(!stagger || rows->steps >= 0, "decode: steps must be >= 0");
   P.steps = (stagger && rows->steps > 0) ? rows->steps : maxlen - 1;
   JANUS_CHECK(!stagger || max_roff + P.steps <= maxlen, "decode: pos_offset + steps > max_length");
@@ -281,9 +294,10 @@ static void plan_paths(DecodePlan& P, const janus_whisper_config& c, const janus
   // (resident grids need every block co-resident: the kernels' occupancy must admit one
   // block per CU of the partition, and a multi-lane call, whose lanes run concurrently on
   // the same CUs, keeps the launch path)
-  // (beam search runs the launch path: a persistent request falls back, as at d_model 768)
+  // (beam search runs the launch path: a persistent request falls back, as at d_model 768;
+  // so does a call with history rules)
   const int seg_grid = P.seg_grid =
-      opt.persistent && !multi_lane && !P.beam_k ? seg.grid(B, cus, path(JANUS_DEC_PATH_SEG_2CU)) : 0;
+      opt.persistent && !multi_lane && !P.beam_k && !P.hist() ? seg.grid(B, cus, path(JANUS_DEC_PATH_SEG_2CU)) : 0;
   const bool persist = seg_grid > 0 && dec_seg_supported(d, H, B, cus) && seg.resident(seg_grid, cus) &&
                        xabs && !P.shared() && !fused_ln && !ln_fuse && !rln && P.ngroups() == 0 && P.npairs() == 0;
   // persistent = 2: segment B of layer l, the self-attention of l + 1 and its segment A as
@@ -329,6 +343,7 @@ std::string DecodePlan::describe() const {
   std::ostringstream o;
   each_scalar([&](const char* n, auto v) { o << n << '=' << +v << '\n'; },
               [&](const char* n, auto v) { o << "call." << n << '=' << +v << '\n'; });
+  if (hist()) o << "repetition_penalty=" << rep_pen << "\nno_repeat_ngram_size=" << ngram << '\n';
   o << "pairs=";
   for (size_t i = 0; i < pairs.size(); ++i)
     o << (i ? "," : "") << pairs[i].b0 << ',' << pairs[i].b1 << ',' << pairs[i].e;

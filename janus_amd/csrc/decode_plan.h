@@ -86,6 +86,9 @@ struct DecodePlan {
   bool use_graph = false;
   int cus = 0, lg_cap = 0, nblk = 0, msplit_n = 0;
   bool sampling = false, row_temps = false;
+  // history rules (janus_decode_options.repetition_penalty / no_repeat_ngram_size): 1 and 0 = off
+  float rep_pen = 1.f;
+  int ngram = 0;
   // ---- host arrays to upload
   std::vector<XPair> pairs;
   std::vector<int> groups;  // [ngroups][8] = {e, row_0 .. row_6 (-1: none)}
@@ -100,6 +103,7 @@ struct DecodePlan {
   int ngroups() const { return (int)groups.size() / 8; }
   bool stagger() const { return !roff.empty(); }
   bool shared() const { return enc_rows != JANUS_ENC_ROWS_OWN; }
+  bool hist() const { return rep_pen != 1.f || ngram > 0; }
 
   // The scalar fields, once. step(name, value): what a captured position reads — the
   // graph cache key and operator== come from these. call(name, value): what only the code
@@ -126,6 +130,8 @@ struct DecodePlan {
   // the plan's part of the graph cache key (LaneBuffers appends the device pointers)
   void append_key(std::vector<int64_t>& key) const {
     each_scalar([&](const char*, auto v) { key.push_back(key_word(v)); }, [](const char*, auto) {});
+    // the history rules, only on a call that sets them: every other call's key is unchanged
+    if (hist()) { key.push_back(key_word(rep_pen)); key.push_back(key_word(ngram)); }
   }
   bool operator==(const DecodePlan& o) const {
     std::vector<int64_t> a, b;
@@ -134,7 +140,8 @@ struct DecodePlan {
     return a == b;
   }
   // name=value lines (janus_decode_plan_describe): the step fields, the call fields as
-  // call.name, then pairs= and groups= as integer lists
+  // call.name, then pairs= and groups= as integer lists; repetition_penalty= and
+  // no_repeat_ngram_size= lines in front of pairs= only on a call that sets one of them
   std::string describe() const;
 };
 

@@ -92,7 +92,19 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
                            const float* lnx = nullptr, int ldx = 0, const float* ln_g = nullptr,
                            const float* ln_b = nullptr, int max_blocks = 256,
                            const uint32_t* seeds = nullptr, int pos = 0,
-                           const float* row_inv_temp = nullptr, BeamTop* tops = nullptr);
+                           const float* row_inv_temp = nullptr, BeamTop* tops = nullptr,
+                           const uint32_t* hist = nullptr, float rep_pen = 1.f);
+// hist (nullable; greedy and sampling, no beam partials): the rows' history words
+// (history_rules_launch) — a penalised column's logit is scaled by rep_pen (> 0) before the
+// filter, a banned column fails it; the raw statistics stay unpenalised
+// The history words: uint32 [groups of logits_row_group(K) rows][(V + 15) / 16 tiles][rows of
+// the group], bits 0-15 penalised / 16-31 banned columns of the tile. history_words: their
+// count for B rows (zeroed by the caller before a call's first position).
+size_t history_words(int V, int K, int B);
+// one position's update for every row (one block per row, in front of logits_partial_launch
+// at the same pos): tokens [B][ld], plen [B] prompt lengths, n = no_repeat_ngram_size
+void history_rules_launch(const int32_t* tokens, int ld, int pos, const int32_t* plen, int n, int V,
+                          int rg, uint32_t* hist, int B, hipStream_t s);
 // tops (nullable, greedy only; [B][nblk]): the beam instantiation — each partial also
 // carries its block's best kBeamTop allowed entries (BeamTop)
 // R.inv_temp > 0: seeds [B] (device) per-row noise seeds, pos = the position whose logits

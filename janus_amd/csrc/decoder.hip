@@ -401,20 +401,27 @@ int logits_partial_blocks(int V, int K, int max_blocks) {
 // of a group in LDS. K = 1280 (the large-v3 family): 64 rows x 1296 halves are 166 KB, more
 // than a CU's 160 KB, so a group is 32 rows (MT = 2: 83 KB of A, 17 KB of patches) and lanes
 // 32 - 63 idle in the statistics pass; the weights are read once per 32-row group.
-template <int NKS, int NB, bool SAMPLE, bool BEAM = false, int MT = 4>  // K / 32
+// HIST (repetition penalty / no-repeat n-grams, janus_decode_options): the row's history word of
+// the tile (history_rules_kernel: bits 0-15 penalised, 16-31 banned columns) arrives with the
+// next tile's weights; a penalised column's logit is scaled (x p below 0, / p otherwise)
+// before the filter, a banned column fails it like a suppressed token. The raw statistics
+// (t_v, m_raw, s_raw) stay on the unpenalised logits; a lane whose word is 0 runs the
+// sibling's epilogue unchanged (the plain tile's shortcut included).
+template <int NKS, int NB, bool SAMPLE, bool BEAM = false, int MT = 4, bool HIST = false>  // K / 32
 __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel(
     const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W, int V, int B,
     DecodeRules R, const uint8_t* __restrict__ smask, const RowRules* __restrict__ rules,
     LogitPart* __restrict__ parts, int ntiles, const float* __restrict__ lnx, int ldx,
     const float* __restrict__ ln_g, const float* __restrict__ ln_b, int rot,
     const uint32_t* __restrict__ seeds, int pos, const float* __restrict__ rinv,
-    BeamTop* __restrict__ tops) {
+    BeamTop* __restrict__ tops, const uint32_t* __restrict__ hist, float rep_pen) {
   extern __shared__ __attribute__((aligned(16))) _Float16 lg_smem[];
   dec_wave_prio();
   // row group blockIdx.y: rows [RG y, RG y + RG) of the call (one launch for every group:
   // a group's blocks start while the previous group's last blocks drain)
   constexpr int RG = 16 * MT;
   static_assert(!BEAM || MT == 4, "the beam merge is laid out for 64-row groups");
+  static_assert(!(HIST && BEAM), "beam search takes no history rules");
   {
     const int r0 = (int)blockIdx.y * RG;
     A += (int64_t)r0 * lda;
@@ -424,6 +431,7 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
     if (seeds) seeds += r0;
     if (rinv) rinv += r0;
     if (BEAM) tops += (int64_t)r0 * gridDim.x;
+    if constexpr (HIST) hist += (int64_t)blockIdx.y * ntiles * RG;   // [group][tile][RG]
     B = min(RG, B - r0);
   }
   constexpr int K = NKS * 32;
@@ -437,6 +445,7 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
   // do not depend on it); later tiles' loads are issued before the previous epilogue
   half8 bw[NB][NKS];
   uint4 sm16[NB];
+  uint32_t hw[NB];   // HIST: the history word of row = lane for the tile (one coalesced load)
   // logical tile t -> physical tile (t + rot) mod ntiles (see logits_partial_launch)
   auto phys = [&](int t) { const int q = t + rot; return q >= ntiles ? q - ntiles : q; };
 #define LG_LOAD(BUF, TILE)                                                                    \
@@ -447,6 +456,7 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
       bw[BUF][ks] = *reinterpret_cast<const half8*>(wrow_ + 32 * ks);                         \
     /* 16 mask bytes per tile (the mask buffer is padded to a multiple of 16) */             \
     sm16[BUF] = *reinterpret_cast<const uint4*>(smask + phys(TILE) * 16);                     \
+    if constexpr (HIST) hw[BUF] = hist[(int64_t)phys(TILE) * RG + (RG < 64 ? min(lane, RG - 1) : lane)]; \
   } while (0)
   const int tile0 = blockIdx.x * kLgWaves + w;
   const int stride = gridDim.x * kLgWaves;
@@ -557,6 +567,10 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
 #pragma unroll
       for (int r = 0; r < 4; ++r) patch[(16 * m + 4 * (lane >> 4) + r) * 17 + lr] = acc[m][r];
     const uint4 smc = sm16[u];
+    uint32_t hwd = 0;
+    if constexpr (HIST) hwd = hw[u];
+    // a penalised column's logit (rule 1 of janus_decode_options), fp32
+    auto penal = [&](float v) { return v < 0.f ? v * rep_pen : v / rep_pen; };
     // the tile NB strides ahead into the registers just consumed, during the epilogue
     if (tile + NB * stride < ntiles) LG_LOAD(u, tile + NB * stride);
     // wave-private patch: the wave's own stores are visible to its loads in order
@@ -584,14 +598,28 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
         t_raw = fmaxf(t_raw, v);
         if (col0 + c == R.target) t_v = v;
         const unsigned smw = c < 4 ? smc.x : c < 8 ? smc.y : c < 12 ? smc.z : smc.w;
-        const bool ok = row_ok && !((smw >> (8 * (c & 3))) & 0xffu);
+        bool ok = row_ok && !((smw >> (8 * (c & 3))) & 0xffu);
+        float pv = v;
+        if constexpr (HIST) {
+          ok = ok && !((hwd >> (16 + c)) & 1u);
+          if ((hwd >> c) & 1u) pv = penal(v);
+        }
         okm |= (unsigned)ok << c;
-        if (ok) t_all = fmaxf(t_all, v);
+        if (ok) t_all = fmaxf(t_all, pv);
       }
       t_text = t_all;
 #pragma unroll
       for (int c = 0; c < 16; ++c) u_raw += __expf(vals[c] - t_raw);
-      if (okm == 0xffffu) {
+      bool full = okm == 0xffffu;
+      if constexpr (HIST) {   // the raw sum is done: the penalised logits take its registers
+        if (hwd & 0xffffu) {
+          full = false;
+#pragma unroll
+          for (int c = 0; c < 16; ++c)
+            if ((hwd >> c) & 1u) vals[c] = penal(vals[c]);
+        }
+      }
+      if (full) {
         u_all = u_raw;
       } else {
 #pragma unroll
@@ -624,16 +652,28 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
         if (t == R.target) t_v = v;
         const unsigned smw = c < 4 ? smc.x : c < 8 ? smc.y : c < 12 ? smc.z : smc.w;
         const bool masked = (smw >> (8 * (c & 3))) & 0xffu;
-        const bool ok = row < B && t < V && !masked && allowed_unmasked(t, R, rr, false);
+        bool ok = row < B && t < V && !masked && allowed_unmasked(t, R, rr, false);
+        float pv = v;
+        if constexpr (HIST) {
+          ok = ok && !((hwd >> (16 + c)) & 1u);
+          if ((hwd >> c) & 1u) pv = penal(v);
+        }
         okm |= (unsigned)ok << c;
         if (ok) {
-          t_all = fmaxf(t_all, v);
-          if (R.ts_begin >= 0 && t >= R.ts_begin) t_ts = fmaxf(t_ts, v);
-          else t_text = fmaxf(t_text, v);
+          t_all = fmaxf(t_all, pv);
+          if (R.ts_begin >= 0 && t >= R.ts_begin) t_ts = fmaxf(t_ts, pv);
+          else t_text = fmaxf(t_text, pv);
         }
       }
 #pragma unroll
       for (int c = 0; c < 16; ++c) u_raw += (col0 + c < V) ? __expf(vals[c] - t_raw) : 0.f;
+      if constexpr (HIST) {
+        if (hwd & 0xffffu) {
+#pragma unroll
+          for (int c = 0; c < 16; ++c)
+            if ((hwd >> c) & 1u) vals[c] = penal(vals[c]);
+        }
+      }
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
         if (!((okm >> c) & 1u)) continue;
@@ -738,8 +778,10 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
                            const DecodeRules& R, const uint8_t* smask, const RowRules* rules,
                            LogitPart* parts, hipStream_t s, const float* lnx, int ldx,
                            const float* ln_g, const float* ln_b, int max_blocks,
-                           const uint32_t* seeds, int pos, const float* row_inv_temp, BeamTop* tops) {
+                           const uint32_t* seeds, int pos, const float* row_inv_temp, BeamTop* tops,
+                           const uint32_t* hist, float rep_pen) {
   JANUS_CHECK(!tops || !(R.inv_temp > 0.f), "logits: the beam partials are greedy only");
+  JANUS_CHECK(!hist || (!tops && rep_pen > 0.f), "logits: history rules need a penalty > 0 and no beam partials");
   JANUS_CHECK(K == 384 || K == 512 || K == 768 || K == 1280, "logits: K (d_model) must be 384, 512, 768 or 1280");
   // K = 1280: 32-row groups (64 rows of A do not fit a CU's LDS), greedy and sampling only
   const bool k1280 = K == 1280;
@@ -757,8 +799,16 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
                        : (K == 384 ? logits_partial_kernel<12, 1, false> : K == 512 ? logits_partial_kernel<16, 1, false>
                                                                            : logits_partial_kernel<24, 1, false>);
   if (k1280) kern = sample ? logits_partial_kernel<40, 1, true, false, 2> : logits_partial_kernel<40, 1, false, false, 2>;
-  static bool attr[11] = {false, false, false, false, false, false, false, false, false, false, false};
-  const int ai = k1280 ? 9 + (int)sample : (K == 384 ? 0 : K == 512 ? 1 : 2) + (tops ? 6 : sample ? 3 : 0);
+  if (hist) {
+    kern = sample ? (K == 384 ? logits_partial_kernel<12, 1, true, false, 4, true> : K == 512 ? logits_partial_kernel<16, 1, true, false, 4, true>
+                                                                               : logits_partial_kernel<24, 1, true, false, 4, true>)
+                  : (K == 384 ? logits_partial_kernel<12, 1, false, false, 4, true> : K == 512 ? logits_partial_kernel<16, 1, false, false, 4, true>
+                                                                                : logits_partial_kernel<24, 1, false, false, 4, true>);
+    if (k1280) kern = sample ? logits_partial_kernel<40, 1, true, false, 2, true> : logits_partial_kernel<40, 1, false, false, 2, true>;
+  }
+  static bool attr[19] = {};
+  const int ai = hist ? 11 + (K == 384 ? 0 : K == 512 ? 1 : K == 768 ? 2 : 3) + (sample ? 4 : 0)
+                      : k1280 ? 9 + (int)sample : (K == 384 ? 0 : K == 512 ? 1 : 2) + (tops ? 6 : sample ? 3 : 0);
   if (!attr[ai]) {
     JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024));
@@ -784,8 +834,62 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
   // 64 (K = 1280: 32) rows per row group (blockIdx.y), every group in one launch
   kern<<<dim3(grid, (B + rg - 1) / rg), nw * 64, lds, s>>>(A, lda, W, V, B, R, smask, rules, parts, ntiles, lnx, ldx,
                                                       ln_g, ln_b, rot, seeds, pos,
-                                                      sample ? row_inv_temp : nullptr, tops);
+                                                      sample ? row_inv_temp : nullptr, tops, hist, rep_pen);
   JANUS_LAUNCH_CHECK();
+}
+
+// ------------------------------------------------------- row history (HIST logits kernel)
+// The history words of one row at position pos, from the tokens it has sampled in this call,
+// g = tokens[plen .. pos] (m = pos + 1 - plen of them): hist [group][tile][rg] uint32, row b in
+// group b / rg, bits 0-15 of a word the penalised columns of the 16-column tile, 16-31 the
+// banned ones (rule of janus_decode_options). One block per row, launched once per position in
+// front of the vocabulary projection: the token at pos joins the penalised set; the bans of
+// position pos - 1 (recomputed from g without its last token) are cleared, then those of pos
+// set: every start i <= m - n whose n - 1 tokens equal the last n - 1 of g bans g[i + n - 1]
+// (n = 1: every token of g). A row inside its prompt does nothing.
+__global__ __launch_bounds__(256) void history_rules_kernel(
+    const int32_t* __restrict__ tokens, int ld, int pos, const int32_t* __restrict__ plen, int n, int V,
+    int ntiles, int rg, uint32_t* __restrict__ hist) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int pl = plen[b];
+  const int m = pos + 1 - pl;
+  if (m <= 0 || pos >= ld) return;  // block-uniform
+  const int32_t* g = tokens + (int64_t)b * ld + pl;
+  uint32_t* words = hist + (int64_t)(b / rg) * ntiles * rg + (b % rg);
+  auto word = [&](int t) { return words + (int64_t)(t >> 4) * rg; };
+  if (tid == 0) {
+    const int t = g[m - 1];
+    if (t >= 0 && t < V) atomicOr(word(t), 1u << (t & 15));
+  }
+  if (n <= 0) return;
+  // the bans of a history of mm tokens, set or cleared
+  auto bans = [&](int mm, bool set) {
+    for (int i = tid; i + n <= mm; i += blockDim.x) {
+      bool eq = true;
+      for (int j = 0; j + 1 < n; ++j) eq = eq && g[i + j] == g[mm - n + 1 + j];
+      const int t = g[i + n - 1];
+      if (!eq || t < 0 || t >= V) continue;
+      if (set) atomicOr(word(t), 0x10000u << (t & 15));
+      else atomicAnd(word(t), ~(0x10000u << (t & 15)));
+    }
+  };
+  bans(m - 1, false);
+  __syncthreads();  // (every clear issued and complete before a set of the same word)
+  bans(m, true);
+}
+
+void history_rules_launch(const int32_t* tokens, int ld, int pos, const int32_t* plen, int n, int V,
+                          int rg, uint32_t* hist, int B, hipStream_t s) {
+  JANUS_CHECK(tokens && plen && hist, "history_rules: null argument");
+  JANUS_CHECK(B >= 1 && n >= 0 && V >= 1 && pos >= 0 && pos < ld && (rg == 32 || rg == 64),
+              "history_rules: need B >= 1, n >= 0, 0 <= pos < ld, row groups of 32 or 64");
+  history_rules_kernel<<<B, 256, 0, s>>>(tokens, ld, pos, plen, n, V, (V + 15) / 16, rg, hist);
+  JANUS_LAUNCH_CHECK();
+}
+
+size_t history_words(int V, int K, int B) {
+  const int rg = logits_row_group(K);
+  return (size_t)((B + rg - 1) / rg) * ((V + 15) / 16) * rg;
 }
 
 

@@ -304,6 +304,42 @@ extern "C" int janus_logits_partial_f16(const uint16_t* A, const uint16_t* W, in
   });
 }
 
+// ------------------------------------------------------------------ history rules
+extern "C" int janus_history_words(int V, int K, int batch) {
+  return V >= 1 && batch >= 1 ? (int)history_words(V, K, batch) : 0;
+}
+
+extern "C" int janus_history_rules(const int32_t* tokens, int ld, int batch, const int32_t* plen, int n, int V,
+                                   int K, int pos0, int n_pos, uint32_t* hist, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(tokens && plen && hist, "null argument");
+    JANUS_CHECK(batch >= 1 && batch <= kSkinnyMaxRows, "history_rules: 1 <= batch <= 512");
+    JANUS_CHECK(pos0 >= 0 && n_pos >= 1 && pos0 + n_pos <= ld, "history_rules: positions outside the token rows");
+    for (int pos = pos0; pos < pos0 + n_pos; ++pos)
+      history_rules_launch(tokens, ld, pos, plen, n, V, logits_row_group(K), hist, batch, (hipStream_t)stream);
+  });
+}
+
+extern "C" int janus_logits_partial_hist_f16(const uint16_t* A, const uint16_t* W, int K, int V, int batch,
+                                             int eot, int suppress_blank, int blank, int ts_begin,
+                                             int no_timestamps, int max_initial_ts, int target,
+                                             const uint8_t* smask, const int32_t* row_rules, int max_blocks,
+                                             float inv_temp, const uint32_t* seeds, int pos, void* parts,
+                                             const uint32_t* hist, float repetition_penalty, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(A && W && smask && row_rules && parts && hist, "null argument");
+    JANUS_CHECK(batch >= 1 && batch <= kSkinnyMaxRows, "logits_partial: 1 <= batch <= 512");
+    JANUS_CHECK(repetition_penalty > 0.f, "logits_partial_hist: repetition_penalty must be > 0");
+    DecodeRules R = beam_rules(eot, suppress_blank, blank, ts_begin, no_timestamps, max_initial_ts);
+    R.target = target;
+    R.inv_temp = inv_temp > 0.f ? inv_temp : 0.f;
+    logits_partial_launch(reinterpret_cast<const _Float16*>(A), K, reinterpret_cast<const _Float16*>(W), K, V,
+                          batch, R, smask, reinterpret_cast<const RowRules*>(row_rules),
+                          static_cast<LogitPart*>(parts), (hipStream_t)stream, nullptr, 0, nullptr, nullptr,
+                          max_blocks, seeds, pos, nullptr, nullptr, hist, repetition_penalty);
+  });
+}
+
 extern "C" int janus_beam_step(const void* parts, const void* tops, int nblk, int eot, int suppress_blank,
                                int blank, int ts_begin, int no_timestamps, int max_initial_ts,
                                int32_t* row_rules, int32_t* tokens, int ld, int pos, int32_t* done,

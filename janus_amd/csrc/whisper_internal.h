@@ -34,7 +34,8 @@ struct DecLane {
   DevMem d_x, d_a, d_qkv, d_o, d_q2, d_f, d_kc, d_vc, d_ck, d_cv, d_smask, d_done, d_prompt, d_nsp,
       d_supp, d_part_o, d_part_ml, d_parts, d_rules, d_tok, d_ntok, d_slp, d_lnp, d_lncnt, d_xqk,
       d_xc, d_xpc, d_xpml, d_enc, d_seed, d_xpairs, d_xgroups, d_roff, d_omid, d_segbar, d_segerr,
-      d_itemp, d_btop, d_bint, d_bfin, d_bfs;   // (beam search: partial tops, window state, finished list)
+      d_itemp, d_btop, d_bint, d_bfin, d_bfs,   // (beam search: partial tops, window state, finished list)
+      d_hist;                                   // (history rules: the rows' penalised / banned bit sets)
   std::map<std::vector<int64_t>, hipGraphExec_t> graphs;
   std::map<std::vector<int64_t>, size_t> graph_nodes;  // kernel nodes per captured graph
   // the path the last decode call took (janus_whisper_decode_path): how its rows reached

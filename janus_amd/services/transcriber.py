@@ -60,7 +60,8 @@ from .. import _native as nat
 from ..common import wavio
 from ..tokenizer import LANGUAGES, SOT_PREV, TASKS
 from ..whisper import (CONFIGS, WhisperEngine, check_beam_args, check_encoder_compute,
-                       check_family_features, resolve_model, shared_rows_in_place)
+                       check_family_features, check_history_args, resolve_model,
+                       resolve_suppress_tokens, shared_rows_in_place)
 from . import vad_filter as vf
 
 WINDOW_16K = 480000
@@ -414,6 +415,32 @@ def window_text_tokens(tk, tokens, seek, size):
     return [t for (_, _, part) in segs for t in part if t < tk.eot]
 
 
+def encode_prompt(tk, prompt, n_vocab: int = None):
+    """faster-whisper's encoding of ``initial_prompt`` / ``hotwords``: a string becomes the
+    tokens of " " + s.strip(), an iterable of token ids is taken as given; None: no tokens."""
+    if prompt is None:
+        return []
+    if isinstance(prompt, str):
+        return [int(t) for t in tk.encode_text(" " + prompt.strip())]
+    ids = [int(t) for t in prompt]
+    if any(t < 0 or (n_vocab is not None and t >= n_vocab) for t in ids):
+        raise ValueError("prompt token ids outside the vocabulary")
+    return ids
+
+
+def decode_option_kwargs(repetition_penalty=1, no_repeat_ngram_size=0, suppress_tokens=(-1,)):
+    """The decode_ex keywords of the options that differ from faster-whisper's defaults (none
+    at the defaults: such a call is exactly the call without them)."""
+    kw = {}
+    if repetition_penalty != 1:
+        kw["repetition_penalty"] = float(repetition_penalty)
+    if no_repeat_ngram_size:
+        kw["no_repeat_ngram_size"] = int(no_repeat_ngram_size)
+    if suppress_tokens is not None and list(suppress_tokens) != [-1]:
+        kw["suppress_tokens"] = [int(t) for t in suppress_tokens]
+    return kw
+
+
 class _Stream:
     """generate_segments state of one utterance."""
 
@@ -421,8 +448,9 @@ class _Stream:
         self.audio = audio16k
         self.content_frames = len(audio16k) // HOP if content_frames is None else int(content_frames)
         self.seek = 0
-        self.all_tokens = []
+        self.all_tokens = []           # (seeded with initial_prompt's tokens)
         self.prompt_reset_since = 0
+        self.hotwords = []             # hotwords' tokens: after <|startofprev|> in every window
         self.segments = []
         self.windows = self.fallbacks = self.skips = 0
         self.fallback_decodes = 0      # sampled decodes (temperature steps) run
@@ -459,8 +487,12 @@ class _Stream:
         return min(N_FRAMES, self.content_frames - self.seek)
 
     def prompt(self, tk, max_length=448):
+        """faster-whisper's get_prompt (no prefix): <|startofprev|>, the hotwords, the last
+        max_length // 2 - 1 previous tokens — when there are hotwords or previous tokens —
+        then the start sequence."""
         prev = self.all_tokens[self.prompt_reset_since:]
-        p = ([getattr(tk, "sot_prev", SOT_PREV)] + prev[-(max_length // 2 - 1):]) if prev else []   # 223 at 448
+        hot = self.hotwords[:max_length // 2 - 1]
+        p = ([getattr(tk, "sot_prev", SOT_PREV)] + hot + prev[-(max_length // 2 - 1):]) if (prev or hot) else []   # 223 at 448
         return p + list(self.sot_sequence if self.sot_sequence is not None else tk.sot_sequence)
 
     def vote_language(self, tk, probs, segments: int, threshold: float, last: bool):
@@ -557,7 +589,9 @@ def settle_round(engine, tk, rows, prompts, keys, enc, max_length, temperatures=
 
 
 def advance(tk, s, size, c0, r, nd, sampled: int = 0, word_timestamps: bool = False, alignment=None,
-            prepend_punctuations=PREPEND_PUNCTUATIONS, append_punctuations=APPEND_PUNCTUATIONS):
+            prepend_punctuations=PREPEND_PUNCTUATIONS, append_punctuations=APPEND_PUNCTUATIONS,
+            condition_on_previous_text: bool = True,
+            prompt_reset_on_temperature: float = PROMPT_RESET_ON_TEMPERATURE):
     """generate_segments' update of one utterance after its window [seek, seek + size) settled
     (c0: the T = 0 Candidate, r: the settled one, nd: sampled re-decodes, sampled: tokens the
     T = 0 decode emitted): the counters, the no-speech skip, the segments (start == end or
@@ -605,8 +639,8 @@ def advance(tk, s, size, c0, r, nd, sampled: int = 0, word_timestamps: bool = Fa
     s.window_seeks.append((s.seek, size, nseek))
     s.seek = nseek
     # condition_on_previous_text: a result settled above prompt_reset_on_temperature
-    # restarts the prompt after these segments
-    if r.temperature > PROMPT_RESET_ON_TEMPERATURE:
+    # restarts the prompt after these segments; without it every window does
+    if not condition_on_previous_text or r.temperature > prompt_reset_on_temperature:
         s.prompt_reset_since = len(s.all_tokens)
 
 
@@ -652,7 +686,10 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
                       append_punctuations: str = APPEND_PUNCTUATIONS, language=None,
                       task: str = "transcribe", language_detection_segments: int = 1,
                       language_detection_threshold: float = 0.5, vad_filter: bool = False,
-                      vad_parameters=None, vad=None):
+                      vad_parameters=None, vad=None, repetition_penalty: float = 1,
+                      no_repeat_ngram_size: int = 0, suppress_tokens=(-1,), initial_prompt=None,
+                      hotwords=None, condition_on_previous_text: bool = True,
+                      prompt_reset_on_temperature: float = PROMPT_RESET_ON_TEMPERATURE):
     """faster-whisper's seek loop for several 16 kHz utterances at once: every round
     decodes the current window of each unfinished utterance as one GPU batch (per-row
     prompts), then the temperature fallback of the windows whose gates failed
@@ -688,9 +725,25 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     duration_after_vad), the seek loop runs on that and the segment and word times are
     restored onto the original audio. An utterance without speech yields no segments. Off
     (the default), no VAD call is made and nothing differs.
+    ``repetition_penalty`` / ``no_repeat_ngram_size`` (the history rules, include/janus.h
+    janus_decode_options) and ``suppress_tokens`` (faster-whisper's list) go to
+    every decode of the loop: the T = 0 pass, the sampled fallback and the speculative call;
+    with ``beam_size`` > 1 the two history rules raise NotImplementedError. ``initial_prompt``
+    (a string or token ids) seeds every utterance's previous tokens, so it is trimmed and reset
+    like previous text; ``hotwords`` (the same forms) follow <|startofprev|> in every window's
+    prompt; ``condition_on_previous_text=False`` restarts the previous text after every
+    window; ``prompt_reset_on_temperature`` is the temperature above which a settled window
+    does. A prompt that leaves no position to sample is a ValueError. At the defaults no call
+    and no result differs.
     Returns one _Stream (segments + gate counters) per utterance."""
     check_beam_args(beam_size, length_penalty)
     check_family_features(getattr(engine, "cfg", None), beam_size, word_timestamps)
+    check_history_args(repetition_penalty, no_repeat_ngram_size, beam_size)
+    dec_kw = decode_option_kwargs(repetition_penalty, no_repeat_ngram_size, suppress_tokens)
+    if "suppress_tokens" in dec_kw:   # (ValueError: an id outside the vocabulary, before any GPU work)
+        resolve_suppress_tokens(engine.tokenizer, dec_kw["suppress_tokens"], engine.cfg.n_vocab)
+        if beam_size > 1:
+            raise NotImplementedError("suppress_tokens other than [-1] is not built for beam search")
     if beam_size > 1 and speculative:
         raise NotImplementedError("speculative=True decodes greedily in one call; beam_size > 1 "
                                   "needs speculative=False")
@@ -707,6 +760,11 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
         speeches = [vf.get_speech_timestamps(p, len(a), opts) for p, a in zip(probs, audios)]
         audios = [vf.collect_chunks(a, sp) for a, sp in zip(audios, speeches)]
     streams = [_Stream(a) for a in audios]
+    n_vocab = getattr(getattr(engine, "cfg", None), "n_vocab", None)
+    seed_tokens, hot_tokens = encode_prompt(tk, initial_prompt, n_vocab), encode_prompt(tk, hotwords, n_vocab)
+    for st in streams:
+        st.all_tokens.extend(seed_tokens)
+        st.hotwords = list(hot_tokens)
     if speeches is not None:
         for st, sp in zip(streams, speeches):
             st.speech_chunks = sp
@@ -761,6 +819,9 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
                     grp[j].vote_language(tk, lp[k], language_detection_segments, language_detection_threshold,
                                          last=grp[j].seek + sizes[j] >= grp[j].content_frames)
             prompts = [s.prompt(tk, max_length) for s in grp]
+            if any(len(p) >= max_length for p in prompts):
+                raise ValueError(f"the prompt (initial_prompt / hotwords / previous text and the start "
+                                 f"sequence) leaves no position to sample within max_length {max_length}")
             keys = [(i if utt_keys is None else int(utt_keys[i]), s.windows) for i, s in zip(idx, grp)]
             pres = None
             if spec:
@@ -774,7 +835,7 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
                     eidx += [j] * per_row
                     rprom += [prompts[j]] * per_row
                 out = engine.decode_ex(enc, prompts=rprom, max_length=max_length, temperature=temps,
-                                       seeds=seeds, enc_index=eidx)
+                                       seeds=seeds, enc_index=eidx, **dec_kw)
                 allr = out.rows()
                 t0 = [allr[j * per_row] for j in range(len(grp))]
                 pres = [[allr[j * per_row + 1 + (ti - 1) * best_of: j * per_row + 1 + ti * best_of]
@@ -785,14 +846,18 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
                     out = engine.decode_beam(enc, prompts=prompts, beam_size=beam_size,
                                              length_penalty=length_penalty, max_length=max_length)
                 else:
-                    out = engine.decode_ex(enc, prompts=prompts, max_length=max_length)
+                    out = engine.decode_ex(enc, prompts=prompts, max_length=max_length, **dec_kw)
                 t0 = out.rows()
                 n_tok = out.n_tokens.cpu().numpy()
             first, final, ndec = settle_round(engine, tk, t0, prompts, keys, enc, max_length,
-                                              temperatures, best_of, presampled=pres)
+                                              temperatures, best_of, presampled=pres, **dec_kw)
+            reset_kw = {}
+            if not condition_on_previous_text or prompt_reset_on_temperature != PROMPT_RESET_ON_TEMPERATURE:
+                reset_kw = dict(condition_on_previous_text=bool(condition_on_previous_text),
+                                prompt_reset_on_temperature=float(prompt_reset_on_temperature))
             if not word_timestamps:
                 for s, size, c0r, r, nd, nt in zip(grp, sizes, first, final, ndec, n_tok):
-                    advance(tk, s, size, c0r, r, nd, nt)
+                    advance(tk, s, size, c0r, r, nd, nt, **reset_kw)
                 continue
             texts = [[] if (r.no_speech_prob > NO_SPEECH_THRESHOLD and not r.avg_logprob > LOG_PROB_THRESHOLD)
                      else window_text_tokens(tk, r.tokens, s.seek, size)
@@ -803,7 +868,8 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
             else:
                 al = engine.align(enc, texts, sizes, enc_index=list(range(len(grp))))
             for s, size, c0r, r, nd, nt, a in zip(grp, sizes, first, final, ndec, n_tok, al):
-                advance(tk, s, size, c0r, r, nd, nt, True, a, prepend_punctuations, append_punctuations)
+                advance(tk, s, size, c0r, r, nd, nt, True, a, prepend_punctuations, append_punctuations,
+                        **reset_kw)
     for st in streams:
         if st.speech_chunks:   # times on the collected speech -> times on the original audio
             st.segments = vf.restore_speech_timestamps(st.segments, vf.SpeechTimestampsMap(st.speech_chunks))
@@ -915,7 +981,10 @@ class WhisperModel:
                    append_punctuations: str = APPEND_PUNCTUATIONS,
                    hallucination_silence_threshold=None, language_detection_segments: int = 1,
                    language_detection_threshold: float = 0.5, vad_filter: bool = False,
-                   vad_parameters=None, **_ignored):
+                   vad_parameters=None, repetition_penalty: float = 1, no_repeat_ngram_size: int = 0,
+                   suppress_tokens=(-1,), initial_prompt=None, hotwords=None,
+                   condition_on_previous_text: bool = True, prompt_reset_on_temperature: float = 0.5,
+                   **_ignored):
         """faster-whisper's transcribe: ``beam_size`` 1 (greedy, the reference's call) .. 8
         (beam search at T = 0, DESIGN.md §5k), ``length_penalty`` > 0, ``patience`` 1;
         ``max_length``: the decoder's token limit per window (448). ``word_timestamps``: every
@@ -924,8 +993,13 @@ class WhisperModel:
         ``append_punctuations``; ``hallucination_silence_threshold`` is not built (None only).
         ``vad_filter`` / ``vad_parameters`` (a dict or VadOptions): only the speech the gate
         finds is decoded and every time is restored onto ``audio`` (generate_segments);
-        ``info.duration_after_vad`` is the audio kept, ``info.vad_options`` the options."""
+        ``info.duration_after_vad`` is the audio kept, ``info.vad_options`` the options.
+        ``repetition_penalty``, ``no_repeat_ngram_size``, ``suppress_tokens``, ``initial_prompt``,
+        ``hotwords``, ``condition_on_previous_text`` and ``prompt_reset_on_temperature`` as in
+        faster-whisper (generate_segments): the two history rules need
+        ``beam_size`` 1 (NotImplementedError otherwise, before any GPU work)."""
         check_beam_args(beam_size, length_penalty, patience)
+        check_history_args(repetition_penalty, no_repeat_ngram_size, beam_size)
         check_family_features(getattr(self.engine, "cfg", None), beam_size, word_timestamps)
         if hallucination_silence_threshold is not None:
             raise NotImplementedError("hallucination_silence_threshold is not supported")
@@ -943,7 +1017,12 @@ class WhisperModel:
                                language_detection_segments=language_detection_segments,
                                language_detection_threshold=language_detection_threshold,
                                vad_filter=bool(vad_filter), vad_parameters=vad_options,
-                               vad=self._vad() if vad_filter else None)[0]
+                               vad=self._vad() if vad_filter else None,
+                               repetition_penalty=repetition_penalty,
+                               no_repeat_ngram_size=no_repeat_ngram_size, suppress_tokens=suppress_tokens,
+                               initial_prompt=initial_prompt, hotwords=hotwords,
+                               condition_on_previous_text=condition_on_previous_text,
+                               prompt_reset_on_temperature=prompt_reset_on_temperature)[0]
         self._count(st)
         info = TranscriptionInfo(st.language, st.language_probability, len(audio) / 16000.0,
                                  st.all_language_probs, st.duration_after_vad, vad_options)

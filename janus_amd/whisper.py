@@ -112,7 +112,8 @@ class janus_decode_options(ctypes.Structure):
                 ("xattn_splits", ctypes.c_int), ("cu_count", ctypes.c_int),
                 ("state_slot", ctypes.c_int), ("logits_blocks", ctypes.c_int),
                 ("msplit_rows_n", ctypes.c_int), ("persistent", ctypes.c_int),
-                ("path_flags", ctypes.c_uint32), ("lanes", ctypes.c_int)]
+                ("path_flags", ctypes.c_uint32), ("lanes", ctypes.c_int),
+                ("repetition_penalty", ctypes.c_float), ("no_repeat_ngram_size", ctypes.c_int)]
 
 
 # janus_decode_options.path_flags (include/janus.h JANUS_DEC_PATH_*): alternative decoder
@@ -327,6 +328,37 @@ BEAM_MAX = 8           # largest beam_size (csrc/decoder.h kBeamMax)
 BEAM_MAX_ROWS = 512    # windows x beam_size of one beam decode (kSkinnyMaxRows)
 
 
+def resolve_suppress_tokens(tokenizer, suppress_tokens, n_vocab: int):
+    """faster-whisper's get_suppressed_tokens: None or [-1] is the tokenizer's default set
+    (the non-speech tokens and the five always-suppressed specials); a list holding -1 is that
+    set plus the list's other ids; a list without -1 (or []) is the list plus the five
+    specials. Sorted ids; ValueError for an id outside the vocabulary."""
+    if suppress_tokens is None:
+        return list(tokenizer.suppress_tokens())
+    ids = [int(t) for t in suppress_tokens]
+    bad = [t for t in ids if t != -1 and not 0 <= t < n_vocab]
+    if bad:
+        raise ValueError(f"suppress_tokens: ids {bad} outside the vocabulary (0 .. {n_vocab - 1})")
+    s = set(t for t in ids if t >= 0)
+    if -1 in ids:
+        s.update(tokenizer.suppress_tokens())
+    t = tokenizer
+    s.update([t.transcribe, t.translate, t.sot, t.sot_prev, t.sot_lm])
+    return sorted(s)
+
+
+def check_history_args(repetition_penalty, no_repeat_ngram_size, beam_size: int = 1):
+    """The history rules' arguments (include/janus.h janus_decode_options): a penalty > 0
+    (1 = off), an n-gram size >= 0 (0 = off); with beam search neither is built."""
+    if not repetition_penalty > 0:
+        raise ValueError("repetition_penalty must be > 0 (1 = off)")
+    if int(no_repeat_ngram_size) != no_repeat_ngram_size or no_repeat_ngram_size < 0:
+        raise ValueError("no_repeat_ngram_size must be an integer >= 0 (0 = off)")
+    if beam_size > 1 and (repetition_penalty != 1 or no_repeat_ngram_size > 0):
+        raise NotImplementedError("repetition_penalty / no_repeat_ngram_size are not built for beam "
+                                  "search (beam_size > 1): use beam_size=1")
+
+
 def check_beam_args(beam_size, length_penalty=1.0, patience=1):
     """faster-whisper's beam options as this build runs them: beam_size 1 .. 8, patience 1,
     length_penalty > 0. NotImplementedError for a value faster-whisper accepts and this build
@@ -486,10 +518,11 @@ class WhisperEngine:
     def decode_options(self, max_length: int = 448, check_every: int = 16,
                        timestamps: bool = True, xattn_splits: int = 0, cu_count: int = 0,
                        state_slot: int = 0, logits_blocks: int = 0, msplit_rows_n: int = 0,
-                       persistent: int = 0, path_flags: int = 0, lanes: int = 0):
+                       persistent: int = 0, path_flags: int = 0, lanes: int = 0, suppress_tokens=None):
         t = self.tokenizer
         prompt = np.array(t.sot_sequence, np.int32)
-        supp = np.array(t.suppress_tokens(), np.int32)
+        supp = np.array(t.suppress_tokens() if suppress_tokens is None else
+                        resolve_suppress_tokens(t, suppress_tokens, self.cfg.n_vocab), np.int32)
         opt = janus_decode_options()
         opt.prompt = prompt.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
         opt.prompt_len = len(prompt)
@@ -532,7 +565,8 @@ class WhisperEngine:
                   cu_count: int = 0, temperature: float = 0.0, seeds=None, enc_index=None,
                   pos_offset=None, steps: int = 0, state_slot: int = 0, logits_blocks: int = 0,
                   msplit_rows_n: int = 0, persistent: int = 0, path_flags: int = 0,
-                  no_speech_back: int = None):
+                  no_speech_back: int = None, repetition_penalty: float = 1.0,
+                  no_repeat_ngram_size: int = 0, suppress_tokens=None):
         """janus_whisper_decode_greedy_ex: per-row prompts (lists of token ids; None = the
         SOT sequence for every row) and the no-speech probability. Returns a DecodeOut.
         temperature > 0 samples instead (janus_whisper_decode_sample_ex: Gumbel-max over the
@@ -552,8 +586,14 @@ class WhisperEngine:
         (DEC_PATH_*, parity tests). ``no_speech_back``: no_speech_prob is read that many
         positions before each prompt's last one (janus_decode_rows.no_speech_back), where the
         prompt must hold <|startoftranscript|>; None = len(tokenizer.sot_sequence) - 1 (0 on
-        ``*.en``, 2 on a multilingual model)."""
+        ``*.en``, 2 on a multilingual model). ``repetition_penalty`` (> 0, 1 = off) /
+        ``no_repeat_ngram_size`` (>= 0, 0 = off): the history rules over each row's sampled
+        tokens (include/janus.h janus_decode_options), greedy and sampled calls,
+        not staggered ones. ``suppress_tokens``: faster-whisper's list (None or [-1] = the
+        tokenizer's set; with -1: that set plus the ids; without: the ids plus the five
+        always-suppressed specials)."""
         B = enc.shape[0] if enc_index is None else len(enc_index)
+        check_history_args(repetition_penalty, no_repeat_ngram_size)
         if steps < 0:
             raise ValueError("steps must be >= 0")
         if steps and pos_offset is None:
@@ -570,9 +610,11 @@ class WhisperEngine:
             sd = np.ascontiguousarray(np.asarray(seeds, np.uint64) & 0xFFFFFFFF, dtype=np.uint32)
         opt, keep = self.decode_options(max_length, check_every, timestamps, xattn_splits, cu_count,
                                         state_slot, logits_blocks, msplit_rows_n, persistent,
-                                        path_flags)
+                                        path_flags, suppress_tokens=suppress_tokens)
         rows = janus_decode_rows()
         rows.no_speech_token = self.tokenizer.no_speech
+        opt.repetition_penalty = float(repetition_penalty)
+        opt.no_repeat_ngram_size = int(no_repeat_ngram_size)
         po = None
         if pos_offset is not None:
             po = np.ascontiguousarray(np.asarray(pos_offset, np.int32))
