@@ -214,11 +214,15 @@ int janus_unpack(const uint8_t* buf, size_t len, janus_mp_node* nodes, size_t ca
 typedef struct {
   int n_mels;      /* 80; 128 for the large-v3 family (no other value is accepted) */
   int n_audio_ctx; /* 1500 encoder positions (3000 mel frames) */
-  int d_model;     /* 384 tiny, 512 base, 768 small, 1280 large-v3 / large-v3-turbo / distil-large-v3 */
-  int n_heads;     /* d_model / 64: up to 20. At 1280 / 20 heads the decode call runs the launch path
-                      (persistent > 0 reports level 0), rows sharing an encoder row are gathered, every
-                      d_model <= 512 fusion is off, and beam search (janus_whisper_decode_beam_ex),
-                      janus_whisper_align and the int8 encoder are refused (non-zero status) */
+  int d_model;     /* 384 tiny, 512 base, 768 small, 1024 medium.en / distil-medium.en, 1280 large-v3 /
+                      large-v3-turbo / distil-large-v3 */
+  int n_heads;     /* d_model / 64: up to 20. At 1024 / 16 and 1280 / 20 heads the decode call runs the launch
+                      path (persistent > 0 reports level 0), rows sharing an encoder row are gathered, every
+                      d_model <= 512 fusion is off, and beam search (janus_whisper_decode_beam_ex) and the
+                      int8 encoder are refused (non-zero status); janus_whisper_align runs up to d_model 1024
+                      and is refused at 1280. Its default alignment set (every head of the last half of the
+                      decoder layers) must not exceed 64 heads: medium.en's 192 are refused (non-zero status)
+                      until janus_whisper_set_alignment_heads names at most 64 */
   int enc_layers;
   int dec_layers;
   int n_vocab;     /* 51864 for *.en, 51865 multilingual, 51866 the large-v3 family (100 languages) */

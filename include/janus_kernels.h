@@ -149,7 +149,7 @@ int janus_resunit_f16(const uint16_t* x, uint16_t* out, const uint16_t* w1, cons
 
 /*
  * Decoder cross-attention over the encoder output with absorbed K/V projections:
- * for every utterance b and head h (H * 64 == D, D in {384, 512, 768}),
+ * for every utterance b and head h (H * 64 == D, D in {384, 512, 768, 1024, 1280}),
  *   p = softmax_2(qk[b][h] . enc[b]^T)   (base-2 softmax: qk carries log2(e)/8),
  *   out[b][h*D:(h+1)*D] = p . enc[b]
  * qk fp16 [B][H*D], enc fp16 [B][Te][D], out fp16 [B][H*D]; nsplit key splits
@@ -221,7 +221,7 @@ int janus_beam_partial_blocks(int V, int K, int max_blocks);
 /*
  * janus_logits_partial_f16: the vocabulary projection's partials alone, greedy (inv_temp 0) or
  * sampling (inv_temp = 1 / T > 0 with seeds [batch] device uint32 and the position pos):
- * K = 384 / 512 / 768 (64-row groups) or 1280 (32-row groups); parts [batch][nblk] x 56 B as
+ * K = 384 / 512 / 768 (64-row groups), 1024 (48-row groups) or 1280 (32-row groups); parts [batch][nblk] x 56 B as
  * above, nblk = janus_beam_partial_blocks(V, K, max_blocks). target: the token whose raw logit
  * t_v tracks (-1: none).
  */
@@ -234,7 +234,7 @@ int janus_logits_partial_f16(const uint16_t* A, const uint16_t* W, int K, int V,
 /*
  * History rules (janus_decode_options.repetition_penalty / no_repeat_ngram_size), the two kernels
  * alone. The history words: uint32 [groups][(V + 15) / 16 tiles][rg rows], rg = 64 rows per
- * group up to K = 768 and 32 at K = 1280, row b in group b / rg; bits 0-15 of a word are the
+ * group up to K = 768, 48 at K = 1024 and 32 at K = 1280, row b in group b / rg; bits 0-15 of a word are the
  * tile's penalised columns, bits 16-31 its banned ones. janus_history_words returns their
  * count for batch rows (a count, not a status).
  *

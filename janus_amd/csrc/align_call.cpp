@@ -36,7 +36,7 @@ static void align_run(janus_whisper* w, const _Float16* enc, int n_enc, int n_wi
   if (Z.heads.empty()) Z.heads = align_default_heads(c.dec_layers, H);
   const int heads = (int)Z.heads.size() / 2;
   JANUS_CHECK(H <= 32, "align: at most 32 heads per layer");
-  JANUS_CHECK(d <= 768, "align: d_model <= 768 (the alignment pass is not built for the 1280-wide models)");
+  JANUS_CHECK(d <= 1024, "align: d_model <= 1024 (the alignment pass is not built for the 1280-wide models)");
   JANUS_CHECK((int64_t)n_enc * Te < (1ll << 31), "align: too many encoder rows");
   // the previous call's plan backs its uploads: let them finish before it is replaced
   JANUS_HIP(hipStreamSynchronize(s));

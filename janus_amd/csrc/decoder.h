@@ -83,7 +83,7 @@ void rules_init_launch(RowRules* rules, int B, hipStream_t s);
 // (one per block of the launch).
 int logits_partial_blocks(int V, int K, int max_blocks = 256);
 // rows of A one block holds in LDS (the weights are read once per group of that many rows):
-// 64 up to K = 768, 32 at K = 1280
+// 64 up to K = 768, 48 at K = 1024, 32 at K = 1280
 int logits_row_group(int K);
 // lnx: A = LayerNorm(lnx) (fp32 [B][K], eps 1e-5) computed in-block instead of read
 void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K, int V, int B,

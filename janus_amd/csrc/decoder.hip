@@ -370,7 +370,8 @@ void rules_init_launch(RowRules* rules, int B, hipStream_t s) {
 // waves per logits block (16 waves — about one tile per wave — measured 4x slower:
 // 114.7 vs 28.8 us per launch)
 constexpr int lg_waves(int /*K*/) { return 8; }
-int logits_row_group(int K) { return K > 768 ? 32 : 64; }
+constexpr int kLgMt1024 = 3;   // m-tiles per row group at K = 1024 (logits_partial_kernel: 48 rows)
+int logits_row_group(int K) { return K == 1024 ? 16 * kLgMt1024 : K > 768 ? 32 : 64; }
 int logits_partial_blocks(int V, int K, int max_blocks) {
   const int cap = max_blocks > 0 ? max_blocks : 256;  // one per CU of a whole MI355X
   return std::max(1, std::min(cap, ((V + 15) / 16 + lg_waves(K) - 1) / lg_waves(K)));
@@ -400,7 +401,10 @@ int logits_partial_blocks(int V, int K, int max_blocks) {
 // MT: 16-row m-tiles of A per row group (RG = 16 MT rows). 4 up to K = 768: all 64 rows
 // of a group in LDS. K = 1280 (the large-v3 family): 64 rows x 1296 halves are 166 KB, more
 // than a CU's 160 KB, so a group is 32 rows (MT = 2: 83 KB of A, 17 KB of patches) and lanes
-// 32 - 63 idle in the statistics pass; the weights are read once per 32-row group.
+// 32 - 63 idle in the statistics pass; the weights are read once per 32-row group. K = 1024
+// (medium.en): 64 rows x 1040 halves + patches + rules are 169 984 B, 6 KB over; 48 rows
+// (MT = 3) are 128 000 B and read the table 6 times per 256 rows where MT = 2 reads it 8 times
+// (both were timed: DESIGN.md §5q). The LayerNorm prologue is a 64-row-group form only.
 // HIST (repetition penalty / no-repeat n-grams, janus_decode_options): the row's history word of
 // the tile (history_rules_kernel: bits 0-15 penalised, 16-31 banned columns) arrives with the
 // next tile's weights; a penalised column's logit is scaled (x p below 0, / p otherwise)
@@ -464,10 +468,10 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
   for (int u = 0; u < NB; ++u)
     if (tile0 + u * stride < ntiles) LG_LOAD(u, tile0 + u * stride);
   bool ln_here = false;
-  if constexpr (K <= 1024) ln_here = lnx != nullptr;  // (ln_rows_wave: d <= 1024; the launcher checks)
+  if constexpr (K <= 1024 && MT == 4) ln_here = lnx != nullptr;  // (ln_rows_wave: d <= 1024; the launcher checks)
   if (ln_here) {  // A = the decoder's final LayerNorm of x, computed here (one wave per row)
     // wave w: rows w + 8j (j < 8), all loads up front
-    if constexpr (K <= 1024)
+    if constexpr (K <= 1024 && MT == 4)
       ln_rows_wave<(K + 255) / 256, RG / kLgWaves>(lnx, ldx, w, kLgWaves, B, ln_g, ln_b, sA, w, AP, K,
                                                    1e-5f, lane);
   } else {
@@ -782,11 +786,13 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
                            const uint32_t* hist, float rep_pen) {
   JANUS_CHECK(!tops || !(R.inv_temp > 0.f), "logits: the beam partials are greedy only");
   JANUS_CHECK(!hist || (!tops && rep_pen > 0.f), "logits: history rules need a penalty > 0 and no beam partials");
-  JANUS_CHECK(K == 384 || K == 512 || K == 768 || K == 1280, "logits: K (d_model) must be 384, 512, 768 or 1280");
-  // K = 1280: 32-row groups (64 rows of A do not fit a CU's LDS), greedy and sampling only
-  const bool k1280 = K == 1280;
+  JANUS_CHECK(K == 384 || K == 512 || K == 768 || K == 1024 || K == 1280,
+              "logits: K (d_model) must be 384, 512, 768, 1024 or 1280");
+  // K = 1024 / 1280: 48- / 32-row groups (64 rows of A do not fit a CU's LDS), greedy and sampling only
+  const bool k1024 = K == 1024, k1280 = K == 1280;
   const int rg = logits_row_group(K);
-  JANUS_CHECK(!k1280 || (!tops && !lnx), "logits: K = 1280 has no beam partials and no LayerNorm prologue");
+  JANUS_CHECK(!(k1024 || k1280) || (!tops && !lnx),
+              "logits: K = 1024 / 1280 has no beam partials and no LayerNorm prologue");
   const bool sample = R.inv_temp > 0.f;
   JANUS_CHECK(!sample || seeds, "logits: sampling needs per-row seeds");
   const int ntiles = (V + 15) / 16;
@@ -799,15 +805,18 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
                        : (K == 384 ? logits_partial_kernel<12, 1, false> : K == 512 ? logits_partial_kernel<16, 1, false>
                                                                            : logits_partial_kernel<24, 1, false>);
   if (k1280) kern = sample ? logits_partial_kernel<40, 1, true, false, 2> : logits_partial_kernel<40, 1, false, false, 2>;
+  if (k1024) kern = sample ? logits_partial_kernel<32, 1, true, false, kLgMt1024> : logits_partial_kernel<32, 1, false, false, kLgMt1024>;
   if (hist) {
     kern = sample ? (K == 384 ? logits_partial_kernel<12, 1, true, false, 4, true> : K == 512 ? logits_partial_kernel<16, 1, true, false, 4, true>
                                                                                : logits_partial_kernel<24, 1, true, false, 4, true>)
                   : (K == 384 ? logits_partial_kernel<12, 1, false, false, 4, true> : K == 512 ? logits_partial_kernel<16, 1, false, false, 4, true>
                                                                                 : logits_partial_kernel<24, 1, false, false, 4, true>);
     if (k1280) kern = sample ? logits_partial_kernel<40, 1, true, false, 2, true> : logits_partial_kernel<40, 1, false, false, 2, true>;
+    if (k1024) kern = sample ? logits_partial_kernel<32, 1, true, false, kLgMt1024, true> : logits_partial_kernel<32, 1, false, false, kLgMt1024, true>;
   }
-  static bool attr[19] = {};
-  const int ai = hist ? 11 + (K == 384 ? 0 : K == 512 ? 1 : K == 768 ? 2 : 3) + (sample ? 4 : 0)
+  static bool attr[23] = {};
+  const int ai = k1024 ? 19 + (int)sample + (hist ? 2 : 0)
+                 : hist ? 11 + (K == 384 ? 0 : K == 512 ? 1 : K == 768 ? 2 : 3) + (sample ? 4 : 0)
                       : k1280 ? 9 + (int)sample : (K == 384 ? 0 : K == 512 ? 1 : 2) + (tops ? 6 : sample ? 3 : 0);
   if (!attr[ai]) {
     JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -831,7 +840,7 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
     if (rem > 0 && nspec > 0 && rem + nspec + (R.blank >= 0 ? 1 + R.blank / 16 : 0) <= stride)
       rot = ((s0 - rem) % ntiles + ntiles) % ntiles;
   }
-  // 64 (K = 1280: 32) rows per row group (blockIdx.y), every group in one launch
+  // 64 (K = 1024: 48, K = 1280: 32) rows per row group (blockIdx.y), every group in one launch
   kern<<<dim3(grid, (B + rg - 1) / rg), nw * 64, lds, s>>>(A, lda, W, V, B, R, smask, rules, parts, ntiles, lnx, ldx,
                                                       ln_g, ln_b, rot, seeds, pos,
                                                       sample ? row_inv_temp : nullptr, tops, hist, rep_pen);
@@ -881,8 +890,8 @@ __global__ __launch_bounds__(256) void history_rules_kernel(
 void history_rules_launch(const int32_t* tokens, int ld, int pos, const int32_t* plen, int n, int V,
                           int rg, uint32_t* hist, int B, hipStream_t s) {
   JANUS_CHECK(tokens && plen && hist, "history_rules: null argument");
-  JANUS_CHECK(B >= 1 && n >= 0 && V >= 1 && pos >= 0 && pos < ld && (rg == 32 || rg == 64),
-              "history_rules: need B >= 1, n >= 0, 0 <= pos < ld, row groups of 32 or 64");
+  JANUS_CHECK(B >= 1 && n >= 0 && V >= 1 && pos >= 0 && pos < ld && (rg == 32 || rg == 48 || rg == 64),
+              "history_rules: need B >= 1, n >= 0, 0 <= pos < ld, row groups of 32, 48 or 64");
   history_rules_kernel<<<B, 256, 0, s>>>(tokens, ld, pos, plen, n, V, (V + 15) / 16, rg, hist);
   JANUS_LAUNCH_CHECK();
 }

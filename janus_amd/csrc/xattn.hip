@@ -815,7 +815,7 @@ void xattn_combine_launch(const float* part_c, const float* part_ml, int nsplit,
 }
 
 bool xattn_supported(int D, int H) {
-  return H * 64 == D && H <= kXCombHeads && (D == 384 || D == 512 || D == 768 || D == 1280);
+  return H * 64 == D && H <= kXCombHeads && (D == 384 || D == 512 || D == 768 || D == 1024 || D == 1280);
 }
 
 // D = 1280, 20 heads: two head groups of 10 per (split, row) in grid.z, 32-key chunks. The E
@@ -839,10 +839,30 @@ static void xattn_1280(const _Float16* qk, const _Float16* enc, int B, int Te, i
   JANUS_LAUNCH_CHECK();
 }
 
+// D = 1024, 16 heads: the heads fill the block's one 16-row MFMA tile, so one block per (split,
+// row) holds them all (no head groups: the encoder row is read once per decoder row), 32-key
+// chunks. The E chunk is 32 x 1040 halves = 66 560 B (72 256 B with P and the scores). Only the
+// split form is built: no PAIR, no DIRECT.
+static void xattn_1024(const _Float16* qk, const _Float16* enc, int B, int Te, int H, int nsplit,
+                       float* part_c, float* part_ml, hipStream_t s) {
+  constexpr int D = 1024, CH = 32;
+  const int chunks = (Te + CH - 1) / CH;
+  const int kps = (chunks + nsplit - 1) / nsplit * CH;
+  auto kern = xattn_kernel<D, CH, false>;
+  static_assert(XGeo<D, CH>::LDS <= 160 * 1024, "xattn 1024: LDS per block");
+  static bool attr = false;
+  if (!attr) {
+    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr = true;
+  }
+  kern<<<dim3(nsplit, B), CH * 8, XGeo<D, CH>::LDS, s>>>(qk, enc, Te, H, kps, part_c, part_ml, nullptr, nullptr, 0);
+  JANUS_LAUNCH_CHECK();
+}
+
 void xattn_launch(const _Float16* qk, const _Float16* enc, int B, int Te, int D, int H,
                   int nsplit, float* part_c, float* part_ml, _Float16* out, hipStream_t s,
                   bool combine, const int4* pairs, int npairs, bool rev) {
-  JANUS_CHECK(xattn_supported(D, H), "xattn: need D = 64 H in {384, 512, 768, 1280}");
+  JANUS_CHECK(xattn_supported(D, H), "xattn: need D = 64 H in {384, 512, 768, 1024, 1280}");
   if (B <= 0 || Te <= 0) return;
   JANUS_CHECK(nsplit >= 1 && nsplit <= 63, "xattn: 1..63 key splits");
   JANUS_CHECK(!pairs || (H <= 8 && npairs >= 1 && D <= 512), "xattn: row pairs need H <= 8, D <= 512");
@@ -856,6 +876,7 @@ void xattn_launch(const _Float16* qk, const _Float16* enc, int B, int Te, int D,
   if (D == 384) xattn_cfg<384, 64>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
   else if (D == 512) xattn_cfg<512, 64>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
   else if (D == 768) xattn_cfg<768, 32>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
+  else if (D == 1024) xattn_1024(qk, enc, B, Te, H, nsplit, part_c, part_ml, s);
   else xattn_1280(qk, enc, B, Te, H, nsplit, part_c, part_ml, s);
   if (!combine) return;  // the caller merges (xattn_combine_vproj_launch)
   if (nsplit <= kXCombMax && D <= 512)

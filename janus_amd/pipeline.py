@@ -31,7 +31,7 @@ from .services.synthesizer import emotion_prompt
 from .services.transcriber import (BEST_OF, HOP, N_FRAMES, TEMPERATURES, _Stream, advance,
                                    gather_windows, settle_round)
 from .vocoder import DEFAULT_REFERENCE_ID, FireflyConfig, VocoderEngine, emotion_id
-from .whisper import CONFIGS, WhisperEngine
+from .whisper import CONFIGS, WhisperEngine, large_family
 
 CAPTURE_RATE = 48000
 
@@ -315,6 +315,11 @@ class JanusPipeline(PacketRenderer):
             raise NotImplementedError(
                 f"JanusPipeline serves the English-only models; the multilingual {model!r} runs "
                 "through services.transcriber.WhisperModel (language / task prompts)")
+        if model in CONFIGS and large_family(CONFIGS[model]):
+            raise NotImplementedError(
+                f"JanusPipeline is not built for the {CONFIGS[model].d_model}-wide {model!r} (its serving "
+                "step runs the d_model <= 768 decoder forms); it runs through "
+                "services.transcriber.WhisperModel")
         super().__init__(vocoder_cfg, vocoder_seed, vocoder_weights)
         self.whisper = WhisperEngine(CONFIGS[model], seed=whisper_seed, encoder_compute=whisper_compute)
         self.max_length = max_length

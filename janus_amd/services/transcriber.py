@@ -737,7 +737,8 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     and no result differs.
     Returns one _Stream (segments + gate counters) per utterance."""
     check_beam_args(beam_size, length_penalty)
-    check_family_features(getattr(engine, "cfg", None), beam_size, word_timestamps)
+    check_family_features(getattr(engine, "cfg", None), beam_size, word_timestamps,
+                          getattr(engine, "alignment_heads", None))
     check_history_args(repetition_penalty, no_repeat_ngram_size, beam_size)
     dec_kw = decode_option_kwargs(repetition_penalty, no_repeat_ngram_size, suppress_tokens)
     if "suppress_tokens" in dec_kw:   # (ValueError: an id outside the vocabulary, before any GPU work)
@@ -897,7 +898,8 @@ class WhisperModel:
     ``effective_compute_type`` reports what runs: ``"float16"`` or ``"int8_float16"``."""
 
     def __init__(self, model_size: str, device: str = "auto", compute_type: str = "default",
-                 *, apply_compute_type: bool = False, vad_weights: dict = None, **_ignored):
+                 *, apply_compute_type: bool = False, vad_weights: dict = None, alignment_heads=None,
+                 **_ignored):
         model_size = resolve_model(model_size)   # ValueError: unknown; "turbo" -> "large-v3-turbo"
         if device not in DEVICES:
             raise ValueError(f"unsupported device {device!r}; one of {DEVICES}")
@@ -905,7 +907,10 @@ class WhisperModel:
         self.model_size = model_size
         self.requested_device, self.requested_compute_type = device, compute_type
         check_encoder_compute(CONFIGS[model_size], enc_compute)   # NotImplementedError: int8 at 1280
-        self.engine = WhisperEngine(CONFIGS[model_size], encoder_compute=enc_compute)
+        # alignment_heads: [(layer, head)] for word_timestamps instead of the default set (needed where
+        # that set exceeds the alignment pass's 64 heads: medium.en's has 192)
+        kw = {} if alignment_heads is None else {"alignment_heads": alignment_heads}
+        self.engine = WhisperEngine(CONFIGS[model_size], encoder_compute=enc_compute, **kw)
         self.stats = {"windows": 0, "needs_fallback": 0, "no_speech_skips": 0, "fallback_decodes": 0}
         # vad_filter: silero weights (default: JANUS_VAD_DIR; none: the energy stand-in); the
         # gate is created on the first transcribe(vad_filter=True)
@@ -1000,7 +1005,8 @@ class WhisperModel:
         ``beam_size`` 1 (NotImplementedError otherwise, before any GPU work)."""
         check_beam_args(beam_size, length_penalty, patience)
         check_history_args(repetition_penalty, no_repeat_ngram_size, beam_size)
-        check_family_features(getattr(self.engine, "cfg", None), beam_size, word_timestamps)
+        check_family_features(getattr(self.engine, "cfg", None), beam_size, word_timestamps,
+                              getattr(self.engine, "alignment_heads", None))
         if hallucination_silence_threshold is not None:
             raise NotImplementedError("hallucination_silence_threshold is not supported")
         self._check_language(language, task)

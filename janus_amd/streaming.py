@@ -31,6 +31,7 @@ from .common.protocol import JanusMode, JanusPacket
 from .services.prosody import YIN_BUF, energy_tag, pitch_tag, prosody_launch
 from .services.transcriber import TEMPERATURES
 from .services.vad import VAD_CENTER_DB, VAD_WIDTH_DB, MultiStreamGate, VoiceActivityDetector
+from .whisper import large_family
 
 CHUNK = 1536                  # audio_io.py:28-31 (48 kHz int16 -> f32 chunks)
 PRE_ROLL_CHUNKS = 10          # engine.py:439
@@ -122,6 +123,12 @@ class StreamingEncoder:
             raise NotImplementedError(
                 "StreamingEncoder serves the English-only models; a multilingual engine runs "
                 "through services.transcriber.WhisperModel (language / task prompts)")
+        wcfg = getattr(whisper, "cfg", None)
+        if large_family(wcfg):
+            raise NotImplementedError(
+                f"StreamingEncoder is not built for the {wcfg.d_model}-wide {wcfg.name!r} (its serving "
+                "step runs the d_model <= 768 decoder forms); it runs through "
+                "services.transcriber.WhisperModel")
         self.device = nat.require_gpu()
         self.temperatures = tuple(float(t) for t in temperatures)
         self.S = n_streams

@@ -59,6 +59,11 @@ CONFIGS = {
     "large-v3-turbo": WhisperConfig("large-v3-turbo", 1280, 20, 32, 4, n_mels=128, n_vocab=tok.N_VOCAB_V3),
     "distil-large-v3": WhisperConfig("distil-large-v3", 1280, 20, 32, 2, n_mels=128, n_vocab=tok.N_VOCAB_V3),
 }
+# the 1024-wide family: d_model 1024, 16 heads, 80 mel bins, the *.en vocabulary; distil keeps
+# medium.en's encoder over a 2-layer decoder. (The multilingual `medium` has the same shapes
+# over 51 865 ids; its name is not registered.)
+CONFIGS["medium.en"] = WhisperConfig("medium.en", 1024, 16, 24, 24)
+CONFIGS["distil-medium.en"] = WhisperConfig("distil-medium.en", 1024, 16, 24, 2)
 MODEL_ALIASES = {"turbo": "large-v3-turbo"}   # faster-whisper's short name
 
 
@@ -71,27 +76,45 @@ def resolve_model(name: str) -> str:
 
 
 def large_family(cfg) -> bool:
-    """The 1280-wide, 20-head models."""
+    """The models past small's width: the 1024-wide, 16-head pair and the
+    1280-wide, 20-head family (§5o). They share the launch path, the gathered shared rows, the
+    row-grouped vocabulary projection (48 / 32 rows) and the refusals of beam search and the
+    int8 encoder."""
     return cfg is not None and getattr(cfg, "d_model", 0) > 768
 
 
-def check_family_features(cfg, beam_size: int = 1, word_timestamps: bool = False) -> None:
-    """What the large-v3 family does not run in this build (second tier):
-    beam search (no beam partials of the vocabulary projection at K = 1280) and word
-    timestamps. NotImplementedError naming the feature, before any GPU work."""
+def wide_name(cfg) -> str:
+    """"1024-wide" / "1280-wide": how a refusal names a large_family() model's width."""
+    return f"{cfg.d_model}-wide"
+
+
+def check_family_features(cfg, beam_size: int = 1, word_timestamps: bool = False, alignment_heads=None) -> None:
+    """What the models past d_model 768 do not run in this build (second
+    tier): beam search (no beam partials of the vocabulary projection at K = 1024 / 1280) and
+    word timestamps — above d_model 1024 always, at 1024 when the alignment set holds more than
+    ALIGN_MAX_HEADS heads. ``alignment_heads``: the engine's named set (None: the default set,
+    every head of the last half of the decoder layers — 192 on medium.en, 16 on
+    distil-medium.en). NotImplementedError naming the feature, before any GPU work."""
     if not large_family(cfg):
         return
     if beam_size > 1:
-        raise NotImplementedError(f"beam_size {beam_size} on {cfg.name}: the 1280-wide models decode "
+        raise NotImplementedError(f"beam_size {beam_size} on {cfg.name}: the {wide_name(cfg)} models decode "
                                   "greedily or sampled (beam_size 1) in this build")
-    if word_timestamps:
+    if word_timestamps and cfg.d_model > 1024:
         raise NotImplementedError(f"word_timestamps on {cfg.name}: the alignment pass is not built for "
                                   "the 1280-wide, 20-head models")
+    if word_timestamps:
+        n = len(alignment_heads) if alignment_heads is not None else len(default_alignment_heads(cfg))
+        if n > ALIGN_MAX_HEADS:
+            raise NotImplementedError(f"word_timestamps on {cfg.name}: its alignment set has {n} heads (the default: "
+                                      f"every head of the last half of the decoder layers) and the alignment pass "
+                                      f"takes at most {ALIGN_MAX_HEADS}; name up to {ALIGN_MAX_HEADS} with "
+                                      "alignment_heads=[(layer, head), ...]")
 
 
 def check_encoder_compute(cfg, mode) -> None:
-    """int8 encoder projections stop at K = 3072 (quant_rows_i8); fc2 of a 1280-wide model
-    has K = 5120: NotImplementedError there."""
+    """int8 encoder projections stop at K = 3072 (quant_rows_i8); fc2 of a 1024- / 1280-wide
+    model has K = 4096 / 5120: NotImplementedError there."""
     if mode in ("int8", ENCODER_COMPUTE["int8"]) and large_family(cfg):
         raise NotImplementedError(f"int8 encoder compute on {cfg.name}: fc2's K = {cfg.ffn} exceeds the "
                                   "int8 path's 3072; these models run float16")
@@ -827,7 +850,8 @@ class WhisperEngine:
         matrix A the path was solved on; ``phases``: janus_whisper_align's measurement mask;
         ``sot_sequences``: one start sequence per window instead of the tokenizer's (a
         multilingual model's per-utterance language and task)."""
-        check_family_features(getattr(self, "cfg", None), word_timestamps=True)
+        check_family_features(getattr(self, "cfg", None), word_timestamps=True,
+                              alignment_heads=getattr(self, "alignment_heads", None))
         t = self.tokenizer
         if len(texts) != len(sizes) or (enc_index is not None and len(enc_index) != len(texts)):
             raise ValueError("align: one text, one size (and one enc_index) per window")
@@ -935,7 +959,7 @@ def shared_rows_in_place(cfg) -> bool:
     sampled batches small (services/transcriber.py FALLBACK_ROWS_GATHER)."""
     if cfg is None:
         return True
-    return cfg.n_heads <= 8 and cfg.d_model <= 512   # (20 heads / 1280: gathered too)
+    return cfg.n_heads <= 8 and cfg.d_model <= 512   # (16 heads / 1024, 20 heads / 1280: gathered too)
 
 
 @dataclasses.dataclass
