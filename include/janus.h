@@ -277,6 +277,41 @@ int janus_whisper_encode(janus_whisper* w, const uint16_t* mel, int batch, uint1
 #define JANUS_ENC_COMPUTE_INT8 1
 int janus_whisper_set_encoder_compute(janus_whisper* w, int mode);
 int janus_whisper_encoder_compute(janus_whisper* w, int32_t* mode);
+/*
+ * Compute type of the decoder's cross-attention operand: the encoder output E the decode
+ * calls are handed. F16 (the default): the cross-attention streams E as given. INT8:
+ * CTranslate2's int8 compute type quantises the input of the cross-attention K / V
+ * projections row by row; here those projections are absorbed into the query, so the same
+ * quantisation lands on E itself:
+ *  1. Every decode call quantises its encoder rows E [n][Te][d] (fp16) once, before its first
+ *     position, per key row t with the int8 encoder's rule: amax = max_j |E[t][j]|,
+ *     q[t][j] = clamp(rint(E[t][j] * (127 / amax)), -127, 127), s[t] = amax / 127; a zero row
+ *     gives q = 0, s = 1.
+ *  2. The cross-attention of every layer, row and position sees
+ *     E'[t][j] = fp16_rn(float(q[t][j]) * s[t]) in place of E[t][j]: the product taken in fp32
+ *     and rounded once to fp16 (numpy: (q.astype(float32) * s[:, None]).astype(float16)). It
+ *     streams q (1 byte per element) and s (4 bytes per key) instead of E (2 bytes).
+ *  3. Everything after that is the fp16 call's arithmetic: scores, softmax, context rows,
+ *     value and output projections.
+ * Honoured by janus_whisper_decode_greedy(_ex), _sample_ex, _sample_rows_ex and _beam_ex (and
+ * the test entry janus_whisper_decode_hidden), shared encoder rows (enc_index: rows read in
+ * place are quantised where they lie, gathered rows gather q and s) and staggered rows (a
+ * continuing call quantises the rows it is handed again) included. A `persistent` request runs
+ * the launch path (janus_whisper_decode_path reports 0), as beam search does.
+ * JANUS_DEC_PATH_NO_XABSORB, JANUS_DEC_PATH_XGROUP and JANUS_DEC_PATH_XROWS(n) with INT8 are
+ * REJECTED (non-zero status, janus_last_error, nothing enqueued), as is a call of more than
+ * 512 rows. janus_whisper_align and janus_whisper_detect_language keep reading the fp16 E
+ * whatever the mode. The mode may be switched between calls, in either direction; F16 again
+ * is bit-identical to a context that never left it. janus_whisper_decode_cross tells which
+ * operand the last decode call read.
+ */
+#define JANUS_CROSS_COMPUTE_F16 0
+#define JANUS_CROSS_COMPUTE_INT8 1
+int janus_whisper_set_cross_compute(janus_whisper* w, int mode);
+int janus_whisper_cross_compute(janus_whisper* w, int32_t* mode);
+/* The JANUS_CROSS_COMPUTE_* the last decode call on this context ran with (the lane
+ * janus_whisper_decode_path reports; JANUS_CROSS_COMPUTE_F16 before any call). */
+int janus_whisper_decode_cross(janus_whisper* w, int32_t* mode);
 
 typedef struct {
   const int32_t* prompt;   /* [host] initial tokens, e.g. {<|startoftranscript|>} for *.en */

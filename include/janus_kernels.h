@@ -293,6 +293,15 @@ int janus_decode_plan_describe(const janus_whisper_config* cfg, const janus_deco
                                int multi_lane, float temperature, const float* temperatures,
                                int beam_size, const int32_t* stand, int n_stand, int stand_maxlen,
                                char* text, int text_cap, int64_t* key, int key_cap, int32_t* n_key);
+/* The same with the context's cross-attention compute type (JANUS_CROSS_COMPUTE_*,
+ * janus_whisper_set_cross_compute) as the call would find it; janus_decode_plan_describe is
+ * this entry at JANUS_CROSS_COMPUTE_F16. */
+int janus_decode_plan_describe_cross(const janus_whisper_config* cfg, const janus_decode_options* opt,
+                                     const janus_decode_rows* rows, int batch, int cus, int resident,
+                                     int multi_lane, float temperature, const float* temperatures,
+                                     int beam_size, const int32_t* stand, int n_stand, int stand_maxlen,
+                                     int cross_compute, char* text, int text_cap, int64_t* key,
+                                     int key_cap, int32_t* n_key);
 
 /*
  * Test-only view of the decoder's residual stream: a teacher-forced run of the decode call's

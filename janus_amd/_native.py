@@ -78,6 +78,9 @@ SIGNATURES = {
     "janus_whisper_encode": [_P, _P, _I32, _P, _P],
     "janus_whisper_set_encoder_compute": [_P, _I32],
     "janus_whisper_encoder_compute": [_P, _P],
+    "janus_whisper_set_cross_compute": [_P, _I32],
+    "janus_whisper_cross_compute": [_P, _P],
+    "janus_whisper_decode_cross": [_P, _P],
     "janus_whisper_decode_greedy": [_P, _P, _I32, _P, _P, _P, _P, _P],
     "janus_whisper_decode_greedy_ex": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
     "janus_whisper_decode_sample_ex": [_P, _P, _I32, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P],
@@ -148,6 +151,8 @@ SIGNATURES = {
     # test-only view of the decode planner (no engine, no device)
     "janus_decode_plan_describe": [_P, _P, _P, _I32, _I32, _I32, _I32, _F32, _P, _I32, _P, _I32, _I32,
                                    _P, _I32, _P, _I32, _P],
+    "janus_decode_plan_describe_cross": [_P, _P, _P, _I32, _I32, _I32, _I32, _F32, _P, _I32, _P, _I32, _I32,
+                                         _I32, _P, _I32, _P, _I32, _P],
     # test-only view of the decoder's residual stream (teacher-forced decode machinery)
     "janus_whisper_decode_hidden": [_P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, _P],
 }

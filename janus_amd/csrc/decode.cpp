@@ -97,6 +97,8 @@ struct LaneBuffers {
   int32_t *bint, *bfin;
   float* bfs;
   uint32_t* hist;                // null: no history rules
+  const int8_t* encq;            // null: the fp16 encoder output (int8 cross-attention: its rows
+  const float* encs;             // quantised, and their per-key scales)
 
   void append_key(std::vector<int64_t>& key) const {
     static_assert(std::is_trivially_copyable<LaneBuffers>::value && sizeof(LaneBuffers) % sizeof(int64_t) == 0 &&
@@ -118,7 +120,11 @@ static LaneBuffers ensure_buffers(janus_whisper* w, DecLane& Z, const DecodePlan
   // the captured decode graphs bake in every pointer they read: the encoder output goes
   // to a context-owned buffer first (one ~0.1 ms device copy) so the graphs are reused
   // whatever buffer the caller's allocator handed out this time
-  Z.d_enc.ensure(sizeof(_Float16) * (int64_t)P.n_enc * Te * d);
+  if (!P.cross_i8) Z.d_enc.ensure(sizeof(_Float16) * (int64_t)P.n_enc * Te * d);
+  if (P.cross_i8) {   // the rows as the cross-attention reads them: int8 and one scale per key
+    Z.d_encq.ensure((int64_t)P.n_enc * Te * d);
+    Z.d_encs.ensure(sizeof(float) * (int64_t)P.n_enc * Te);
+  }
   if (P.npairs() > 0) Z.d_xpairs.ensure(sizeof(int4) * P.npairs());
   if (P.ngroups() > 0) Z.d_xgroups.ensure(sizeof(int) * P.groups.size());
   Z.d_x.ensure(sizeof(float) * B * d);
@@ -202,6 +208,8 @@ static LaneBuffers ensure_buffers(janus_whisper* w, DecLane& Z, const DecodePlan
   b.btop = Z.d_btop.as<BeamTop>(); b.bint = Z.d_bint.as<int32_t>(); b.bfin = Z.d_bfin.as<int32_t>();
   b.bfs = Z.d_bfs.as<float>();
   b.hist = P.hist() ? Z.d_hist.as<uint32_t>() : nullptr;
+  b.encq = P.cross_i8 ? Z.d_encq.as<int8_t>() : nullptr;
+  b.encs = P.cross_i8 ? Z.d_encs.as<float>() : nullptr;
   return b;
 }
 
@@ -226,7 +234,26 @@ static void upload_inputs(janus_whisper* w, DecLane& Z, const DecodePlan& P, con
   const janus_decode_options* opt = call.opt;
   const int B = P.B, maxlen = P.maxlen, f0 = P.f0, f1 = P.f1, V = w->cfg.n_vocab;
   const int64_t erow = (int64_t)w->cfg.n_audio_ctx * w->cfg.d_model;
-  if (P.enc_rows == JANUS_ENC_ROWS_GATHERED) {
+  if (P.cross_i8) {
+    // int8 cross-attention: the call's encoder rows quantised once, per key, from where they
+    // lie (no fp16 copy); gathered rows gather the shared rows' q and s (1 byte per element)
+    const int Te = w->cfg.n_audio_ctx, d = w->cfg.d_model;
+    if (P.enc_rows == JANUS_ENC_ROWS_GATHERED) {
+      const int n_src = call.rows->n_enc;
+      Z.d_encq0.ensure((int64_t)n_src * erow);
+      Z.d_encs0.ensure(sizeof(float) * (int64_t)n_src * Te);
+      quant_rows_i8_launch(call.enc_in, d, Z.d_encq0.as<int8_t>(), d, Z.d_encs0.as<float>(), n_src * Te, d, s);
+      for (int r = 0; r < B; ++r) {
+        const int e = call.rows->enc_index[r];
+        JANUS_HIP(hipMemcpyAsync(Z.d_encq.as<int8_t>() + (int64_t)r * erow, Z.d_encq0.as<int8_t>() + (int64_t)e * erow,
+                                 erow, hipMemcpyDeviceToDevice, s));
+        JANUS_HIP(hipMemcpyAsync(Z.d_encs.as<float>() + (int64_t)r * Te, Z.d_encs0.as<float>() + (int64_t)e * Te,
+                                 sizeof(float) * Te, hipMemcpyDeviceToDevice, s));
+      }
+    } else {
+      quant_rows_i8_launch(call.enc_in, d, Z.d_encq.as<int8_t>(), d, Z.d_encs.as<float>(), P.n_enc * Te, d, s);
+    }
+  } else if (P.enc_rows == JANUS_ENC_ROWS_GATHERED) {
     for (int r = 0; r < B; ++r)
       JANUS_HIP(hipMemcpyAsync(Z.d_enc.as<_Float16>() + (int64_t)r * erow, call.enc_in + (int64_t)call.rows->enc_index[r] * erow,
                                sizeof(_Float16) * erow, hipMemcpyDeviceToDevice, s));
@@ -459,6 +486,9 @@ struct DecodeStep : LaneBuffers {
     } else if (xgroups)
       xattn_group_launch(xqk, enc, Te, d, H, xsplit, xpc, xpml, s,
                          xgroups, ngroups, grp_rows);
+    else if (encq)   // the int8 encoder output (one row, PAIR blocks or one split)
+      xattn_i8_launch(xqk, encq, encs, B, Te, d, H, xsplit, xpc, xpml, xc, s,
+                      !cvp, xpairs, npairs);
     else
       xattn_launch(xqk, enc, B, Te, d, H, xsplit, xpc, xpml, xc, s,
                    !cvp, xpairs, npairs);
@@ -683,7 +713,7 @@ static void decode_lane(janus_whisper* w, DecLane& Z, const DecodeCall& call, in
   lane_check(Z);   // the previous non-polling call's flag first
   const DecodePlan P = plan_decode(w->cfg, *call.opt, call.rows, call.smp, call.beam, B, stream_cu_count(s),
                                    latch != nullptr, LaneStand{&Z.stand, Z.stand_maxlen},
-                                   SegDevice{dec_seg_grid, dec_seg_resident});
+                                   SegDevice{dec_seg_grid, dec_seg_resident}, w->cross_compute);
   // until this call completes, nothing may be continued (a failed call leaves stand empty)
   Z.stand.clear();
   const LaneBuffers b = ensure_buffers(w, Z, P, call.opt->n_suppress, s);
@@ -696,6 +726,7 @@ static void decode_lane(janus_whisper* w, DecLane& Z, const DecodeCall& call, in
   Z.last_launches = 0;
   Z.last_enc_rows = P.enc_rows;
   Z.last_persist = P.persist;
+  Z.last_cross = P.cross_i8 ? JANUS_CROSS_COMPUTE_INT8 : JANUS_CROSS_COMPUTE_F16;
   run_positions(Z, P, b, step, s);
   finish(Z, P, b, call, bst, s);
 }
@@ -738,7 +769,8 @@ static void hidden_lane(janus_whisper* w, DecLane& Z, const DecodeCall& call, in
                         hipStream_t s) {
   lane_check(Z);
   const DecodePlan P = plan_decode(w->cfg, *call.opt, call.rows, nullptr, nullptr, B, stream_cu_count(s), false,
-                                   LaneStand{&Z.stand, Z.stand_maxlen}, SegDevice{dec_seg_grid, dec_seg_resident});
+                                   LaneStand{&Z.stand, Z.stand_maxlen}, SegDevice{dec_seg_grid, dec_seg_resident},
+                                   w->cross_compute);
   JANUS_CHECK(P.steps <= x_positions, "decode_hidden: x_out holds fewer positions than the call runs");
   const std::string desc = P.describe();
   JANUS_CHECK(text && (int64_t)desc.size() < text_cap, "decode_hidden: plan_text too small");
@@ -775,6 +807,7 @@ static void hidden_lane(janus_whisper* w, DecLane& Z, const DecodeCall& call, in
   Z.last_launches = 0;
   Z.last_enc_rows = P.enc_rows;
   Z.last_persist = P.persist;
+  Z.last_cross = P.cross_i8 ? JANUS_CROSS_COMPUTE_INT8 : JANUS_CROSS_COMPUTE_F16;
   Z.stand.assign(B, 0);
   for (int r = 0; r < B; ++r) Z.stand[r] = (P.stagger() ? P.roff[r] : 0) + P.steps;
   Z.stand_maxlen = P.maxlen;
@@ -976,6 +1009,15 @@ extern "C" int janus_whisper_decode_path(janus_whisper* w, int32_t* enc_rows, in
     const int sl = w->last_slot < (int)w->lanes.size() ? w->last_slot : 0;
     *enc_rows = w->lanes.empty() ? JANUS_ENC_ROWS_OWN : w->lanes[sl]->last_enc_rows;
     *persistent = w->lanes.empty() ? 0 : w->lanes[sl]->last_persist;
+  });
+}
+
+extern "C" int janus_whisper_decode_cross(janus_whisper* w, int32_t* mode) {
+  return guarded([&] {
+    JANUS_CHECK(w && mode, "null argument");
+    std::lock_guard<std::mutex> lk(w->mu);
+    const int sl = w->last_slot < (int)w->lanes.size() ? w->last_slot : 0;
+    *mode = w->lanes.empty() ? JANUS_CROSS_COMPUTE_F16 : w->lanes[sl]->last_cross;
   });
 }
 

@@ -296,8 +296,10 @@ static void plan_paths(DecodePlan& P, const janus_whisper_config& c, const janus
   // the same CUs, keeps the launch path)
   // (beam search runs the launch path: a persistent request falls back, as at d_model 768;
   // so does a call with history rules)
+  // (the int8 cross-attention likewise: the persistent levels' one-split forms are not built for it)
   const int seg_grid = P.seg_grid =
-      opt.persistent && !multi_lane && !P.beam_k && !P.hist() ? seg.grid(B, cus, path(JANUS_DEC_PATH_SEG_2CU)) : 0;
+      opt.persistent && !multi_lane && !P.beam_k && !P.hist() && !P.cross_i8
+          ? seg.grid(B, cus, path(JANUS_DEC_PATH_SEG_2CU)) : 0;
   const bool persist = seg_grid > 0 && dec_seg_supported(d, H, B, cus) && seg.resident(seg_grid, cus) &&
                        xabs && !P.shared() && !fused_ln && !ln_fuse && !rln && P.ngroups() == 0 && P.npairs() == 0;
   // persistent = 2: segment B of layer l, the self-attention of l + 1 and its segment A as
@@ -322,9 +324,26 @@ static void plan_paths(DecodePlan& P, const janus_whisper_config& c, const janus
 
 DecodePlan plan_decode(const janus_whisper_config& cfg, const janus_decode_options& opt,
                        const janus_decode_rows* rows, const DecodeSampling* smp, const BeamMode* beam,
-                       int B, int cus, bool multi_lane, const LaneStand& stand, const SegDevice& seg) {
+                       int B, int cus, bool multi_lane, const LaneStand& stand, const SegDevice& seg,
+                       int cross_compute) {
   DecodePlan P;
   P.B = B;
+  // int8 cross-attention (janus_whisper_set_cross_compute): the absorbed launch path's one-row,
+  // PAIR and one-split forms only
+  JANUS_CHECK(cross_compute == JANUS_CROSS_COMPUTE_F16 || cross_compute == JANUS_CROSS_COMPUTE_INT8,
+              "decode: cross_compute must be 0 (float16) or 1 (int8)");
+  if ((P.cross_i8 = cross_compute == JANUS_CROSS_COMPUTE_INT8)) {
+    const uint32_t pf = opt.path_flags;
+    JANUS_CHECK(!(pf & JANUS_DEC_PATH_NO_XABSORB),
+                "decode: JANUS_DEC_PATH_NO_XABSORB with cross_compute int8: the int8 encoder output is read by "
+                "the absorbed cross-attention only");
+    JANUS_CHECK(!(pf & JANUS_DEC_PATH_XGROUP),
+                "decode: JANUS_DEC_PATH_XGROUP with cross_compute int8: GROUP blocks read the fp16 encoder output only");
+    JANUS_CHECK(!((pf >> 18) & 3u),
+                "decode: JANUS_DEC_PATH_XROWS with cross_compute int8: ROWS blocks read the fp16 encoder output only");
+    JANUS_CHECK(xattn_supported(cfg.d_model, cfg.n_heads) && B <= kSkinnyMaxRows,
+                "decode: cross_compute int8 needs the absorbed cross-attention (d_model 384 .. 1280, <= 512 rows)");
+  }
   P.maxlen = opt.max_length;
   P.check_every = opt.check_every;
   P.chunk = opt.check_every > 0 ? opt.check_every : 16;
@@ -344,6 +363,7 @@ std::string DecodePlan::describe() const {
   each_scalar([&](const char* n, auto v) { o << n << '=' << +v << '\n'; },
               [&](const char* n, auto v) { o << "call." << n << '=' << +v << '\n'; });
   if (hist()) o << "repetition_penalty=" << rep_pen << "\nno_repeat_ngram_size=" << ngram << '\n';
+  if (cross_i8) o << "cross_int8=1\n";
   o << "pairs=";
   for (size_t i = 0; i < pairs.size(); ++i)
     o << (i ? "," : "") << pairs[i].b0 << ',' << pairs[i].b1 << ',' << pairs[i].e;

@@ -377,6 +377,17 @@ extern "C" int janus_decode_plan_describe(const janus_whisper_config* cfg, const
                                           int multi_lane, float temperature, const float* temperatures,
                                           int beam_size, const int32_t* stand, int n_stand, int stand_maxlen,
                                           char* text, int text_cap, int64_t* key, int key_cap, int32_t* n_key) {
+  return janus_decode_plan_describe_cross(cfg, opt, rows, batch, cus, resident, multi_lane, temperature,
+                                          temperatures, beam_size, stand, n_stand, stand_maxlen,
+                                          JANUS_CROSS_COMPUTE_F16, text, text_cap, key, key_cap, n_key);
+}
+
+extern "C" int janus_decode_plan_describe_cross(const janus_whisper_config* cfg, const janus_decode_options* opt,
+                                                const janus_decode_rows* rows, int batch, int cus, int resident,
+                                                int multi_lane, float temperature, const float* temperatures,
+                                                int beam_size, const int32_t* stand, int n_stand,
+                                                int stand_maxlen, int cross_compute, char* text, int text_cap,
+                                                int64_t* key, int key_cap, int32_t* n_key) {
   return guarded([&] {
     JANUS_CHECK(cfg && opt && text && key && n_key, "null argument");
     JANUS_CHECK(batch >= 1, "decode: batch must be >= 1");
@@ -389,7 +400,7 @@ extern "C" int janus_decode_plan_describe(const janus_whisper_config* cfg, const
     seg.resident = [resident](int, int) { return resident != 0; };
     const DecodePlan P = plan_decode(*cfg, *opt, rows, (temperatures || temperature > 0.f) ? &smp : nullptr,
                                      beam_size > 0 ? &bm : nullptr, batch, cus, multi_lane != 0,
-                                     LaneStand{&st, stand_maxlen}, seg);
+                                     LaneStand{&st, stand_maxlen}, seg, cross_compute);
     const std::string d = P.describe();
     std::vector<int64_t> k;
     P.append_key(k);

@@ -144,6 +144,13 @@ void xattn_absorb(const float* wq, const float* bq, const float* wk, int D, int 
 void xattn_launch(const _Float16* qk, const _Float16* enc, int B, int Te, int D, int H,
                   int nsplit, float* part_c, float* part_ml, _Float16* out, hipStream_t s,
                   bool combine = true, const int4* pairs = nullptr, int npairs = 0, bool rev = false);
+// xattn_launch over the row-quantised encoder output (quant_rows_i8_launch's q and scale of
+// the fp16 rows): encq int8 [n][Te][D], escale f32 [n][Te]. The kernel sees E'[t][j] =
+// fp16(float(q[t][j]) * s[t]) (fp32 product, rounded once) where xattn_launch sees E; the
+// split form at every width, PAIR and the one-split form up to D = 512.
+void xattn_i8_launch(const _Float16* qk, const int8_t* encq, const float* escale, int B, int Te, int D, int H,
+                     int nsplit, float* part_c, float* part_ml, _Float16* out, hipStream_t s,
+                     bool combine = true, const int4* pairs = nullptr, int npairs = 0);
 // Groups of <= 6 decoder rows sharing an encoder row, one block per (split, group):
 // groups [device] int [ngroups][8] = {e, row_0 .. row_5 (-1: none), -}; partials as
 // xattn_launch(combine = false) writes them (merged by xattn_combine_vproj_launch).

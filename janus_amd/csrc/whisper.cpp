@@ -346,3 +346,24 @@ extern "C" int janus_whisper_encoder_compute(janus_whisper* w, int32_t* mode) {
     *mode = w->enc_compute;
   });
 }
+
+extern "C" int janus_whisper_set_cross_compute(janus_whisper* w, int mode) {
+  return guarded([&] {
+    JANUS_CHECK(w, "null argument");
+    JANUS_CHECK(mode == JANUS_CROSS_COMPUTE_F16 || mode == JANUS_CROSS_COMPUTE_INT8,
+                "cross compute: 0 (float16) or 1 (int8)");
+    if (mode == JANUS_CROSS_COMPUTE_INT8)
+      JANUS_CHECK(xattn_supported(w->cfg.d_model, w->cfg.n_heads),
+                  "int8 cross-attention: d_model must be 384, 512, 768, 1024 or 1280 with 64-wide heads");
+    std::lock_guard<std::mutex> lk(w->mu);
+    w->cross_compute = mode;
+  });
+}
+
+extern "C" int janus_whisper_cross_compute(janus_whisper* w, int32_t* mode) {
+  return guarded([&] {
+    JANUS_CHECK(w && mode, "null argument");
+    std::lock_guard<std::mutex> lk(w->mu);
+    *mode = w->cross_compute;
+  });
+}

@@ -35,12 +35,16 @@ struct DecLane {
       d_supp, d_part_o, d_part_ml, d_parts, d_rules, d_tok, d_ntok, d_slp, d_lnp, d_lncnt, d_xqk,
       d_xc, d_xpc, d_xpml, d_enc, d_seed, d_xpairs, d_xgroups, d_roff, d_omid, d_segbar, d_segerr,
       d_itemp, d_btop, d_bint, d_bfin, d_bfs,   // (beam search: partial tops, window state, finished list)
-      d_hist;                                   // (history rules: the rows' penalised / banned bit sets)
+      d_hist,                                   // (history rules: the rows' penalised / banned bit sets)
+      // int8 cross-attention: the rows' quantised encoder output and per-key scales as the
+      // kernels read them, and the shared rows' before the gather (gathered rows only)
+      d_encq, d_encs, d_encq0, d_encs0;
   std::map<std::vector<int64_t>, hipGraphExec_t> graphs;
   std::map<std::vector<int64_t>, size_t> graph_nodes;  // kernel nodes per captured graph
   // the path the last decode call took (janus_whisper_decode_path): how its rows reached
   // their encoder output (JANUS_ENC_ROWS_*) and the persistent level it ran (0: launches)
   int last_enc_rows = 0, last_persist = 0;
+  int last_cross = 0;            // JANUS_CROSS_COMPUTE_* the last call ran (janus_whisper_decode_cross)
   int last_positions = 0;        // positions the last decode stepped
   int64_t last_launches = 0;     // kernel launches those positions issued (graph nodes)
   // where each row slot stands after the last call (positions whose KV rows and next
@@ -83,6 +87,7 @@ struct janus_whisper {
   bool prepared = false;
   int enc_compute = JANUS_ENC_COMPUTE_F16;  // janus_whisper_set_encoder_compute
   bool i8_prepared = false;                 // the encoder layers hold their int8 weights
+  int cross_compute = JANUS_CROSS_COMPUTE_F16;  // janus_whisper_set_cross_compute
   std::mutex mu;
   // device-side prepared weights
   janus::DevMem conv1p, conv2p, pos16, tok16;

@@ -78,6 +78,21 @@ __global__ __launch_bounds__(CH * 8, (PF2 || HG) ? 1 : 2) void xattn_kernel(
                                                          HG ? (int)blockIdx.z : 0);
 }
 
+// xattn_kernel over the row-quantised encoder output (xattn_body's I8: encq int8 with row pitch
+// D, esc the per-key scales; xattn_i8_launch): the one-deep fragment loads only, so no PF2, no
+// ROWLD. A kernel of its own, so that xattn_kernel's arguments and code stay what they were.
+template <int D, int CH, bool PAIR = false, bool DIRECT = false, int HG = 0>
+__global__ __launch_bounds__(CH * 8, HG ? 1 : 2) void xattn_i8_kernel(
+    const _Float16* __restrict__ qk, const signed char* __restrict__ encq, const float* __restrict__ esc,
+    int Te, int H, int kps, float* __restrict__ part_c, float* __restrict__ part_ml,
+    const int4* __restrict__ pairs, _Float16* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) _Float16 smem[];
+  dec_wave_prio();
+  xattn_body<D, CH, PAIR, DIRECT, false, false, false, HG, true>(
+      qk, reinterpret_cast<const _Float16*>(encq), Te, H, kps, part_c, part_ml, pairs, out, blockIdx.x,
+      gridDim.x, blockIdx.y, smem, false, HG ? (int)blockIdx.z : 0, esc);
+}
+
 // GROUP (r04): up to 2*NMT decoder rows attending to the same encoder row — the best_of = 5
 // sampled hypotheses of one window (faster-whisper's generate_with_fallback) — in ONE
 // block: NMT m-tiles of 16 MFMA rows (8 per decoder row, H <= 8), so the block reads the
@@ -884,6 +899,61 @@ void xattn_launch(const _Float16* qk, const _Float16* enc, int B, int Te, int D,
   else
     xattn_combine_rows(part_c, part_ml, nsplit, B, H, D, out, s);
   JANUS_LAUNCH_CHECK();
+}
+
+// ------------------------------------------------------------ int8 encoder output
+// xattn_launch over the row-quantised encoder output (janus_whisper_set_cross_compute): encq
+// int8 [n][Te][D], escale f32 [n][Te]; the forms the decode call's launch path uses — the split
+// form at every width, PAIR and DIRECT (one split, plain one-deep loads) up to D = 512. The
+// merges are xattn_launch's.
+template <int D, int CH, int HG = 0>
+static void xattn_i8_cfg(const _Float16* qk, const int8_t* encq, const float* escale, int B, int Te, int H,
+                         int nsplit, float* part_c, float* part_ml, hipStream_t s, const int4* pairs,
+                         int npairs, _Float16* out = nullptr) {
+  const int chunks = (Te + CH - 1) / CH;
+  const int kps = (chunks + nsplit - 1) / nsplit * CH;
+  const bool direct = out != nullptr;
+  static_assert(XGeo<D, CH>::LDS <= 160 * 1024, "xattn int8: LDS per block");
+  decltype(&xattn_i8_kernel<D, CH, false, false, HG>) kern;
+  if constexpr (HG != 0 || D > 512) {
+    kern = xattn_i8_kernel<D, CH, false, false, HG>;
+  } else {
+    if (direct) kern = xattn_i8_kernel<D, CH, false, true>;
+    else kern = pairs ? xattn_i8_kernel<D, CH, true> : xattn_i8_kernel<D, CH, false>;
+  }
+  const int ai = direct ? 2 : pairs != nullptr;
+  static bool attr[3] = {false, false, false};
+  if (!attr[ai]) {
+    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr[ai] = true;
+  }
+  constexpr int hg = HG ? HG : 32;   // (no head groups: every head in one block)
+  const dim3 grid(nsplit, pairs ? npairs : B, HG ? (H + hg - 1) / hg : 1);
+  kern<<<grid, CH * 8, XGeo<D, CH>::LDS, s>>>(qk, reinterpret_cast<const signed char*>(encq), escale, Te, H, kps,
+                                              part_c, part_ml, pairs, out);
+  JANUS_LAUNCH_CHECK();
+}
+
+void xattn_i8_launch(const _Float16* qk, const int8_t* encq, const float* escale, int B, int Te, int D, int H,
+                     int nsplit, float* part_c, float* part_ml, _Float16* out, hipStream_t s, bool combine,
+                     const int4* pairs, int npairs) {
+  JANUS_CHECK(xattn_supported(D, H), "xattn: need D = 64 H in {384, 512, 768, 1024, 1280}");
+  JANUS_CHECK(encq && escale, "xattn int8: null encoder rows or scales");
+  if (B <= 0 || Te <= 0) return;
+  JANUS_CHECK(nsplit >= 1 && nsplit <= 63, "xattn: 1..63 key splits");
+  JANUS_CHECK(!pairs || (H <= 8 && npairs >= 1 && D <= 512), "xattn: row pairs need H <= 8, D <= 512");
+  if (combine && nsplit == 1 && !pairs && D <= 512) {   // DIRECT: the kernel writes c itself
+    if (D == 384) xattn_i8_cfg<384, 64>(qk, encq, escale, B, Te, H, 1, part_c, part_ml, s, nullptr, 0, out);
+    else xattn_i8_cfg<512, 64>(qk, encq, escale, B, Te, H, 1, part_c, part_ml, s, nullptr, 0, out);
+    return;
+  }
+  if (D == 384) xattn_i8_cfg<384, 64>(qk, encq, escale, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
+  else if (D == 512) xattn_i8_cfg<512, 64>(qk, encq, escale, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
+  else if (D == 768) xattn_i8_cfg<768, 32>(qk, encq, escale, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
+  else if (D == 1024) xattn_i8_cfg<1024, 32>(qk, encq, escale, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
+  else xattn_i8_cfg<1280, 32, 10>(qk, encq, escale, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
+  if (!combine) return;  // the caller merges (xattn_combine_vproj_launch)
+  xattn_combine_launch(part_c, part_ml, nsplit, B, H, D, out, s);
 }
 
 }  // namespace janus

@@ -7,6 +7,7 @@
 namespace janus {
 
 typedef short short4v __attribute__((ext_vector_type(4)));
+typedef unsigned int xu32x2 __attribute__((ext_vector_type(2)));   // 8 int8 as loaded
 
 // ------------------------------------------------------------ attention over enc
 // Contraction order of a chunk's 32 keys in the P.E product: MFMA k index
@@ -62,11 +63,19 @@ struct XGeo {
 // HG (> 16 heads: the 20-head family at D = 1280): the heads go out in groups of HG <= 16
 // per block — block hz of gridDim.z holds heads [HG hz, HG hz + HG) in its MFMA rows and reads
 // the encoder row itself, so E is read once per head group; 0: every head in one block.
-template <int D, int CH, bool PAIR, bool DIRECT, bool PF2, bool SC1Q = false, bool ROWLD = false, int HG = 0>
+// I8 (int8 encoder output, janus_whisper_set_cross_compute): enc is the row-quantised output,
+// int8 [n][Te][D] with row pitch D, and esc [n][Te] its per-key scales. A lane's fragment belongs
+// to one key, so a chunk's loads are 8 B per slot (not 16) plus one f32; each slot becomes
+// the half8 of E'[t][j] = fp16(float(q[t][j]) * s[t]) in registers (the product in fp32, rounded
+// once) at the head of its chunk, once the loads have had the previous chunk's softmax and P.E
+// to arrive. The S phase, the sE staging, the softmax and P.E are the fp16 form's, on E'.
+template <int D, int CH, bool PAIR, bool DIRECT, bool PF2, bool SC1Q = false, bool ROWLD = false, int HG = 0,
+          bool I8 = false>
 __device__ __forceinline__ void xattn_body(
     const _Float16* __restrict__ qk, const _Float16* __restrict__ enc, int Te, int H, int kps,
     float* __restrict__ part_c, float* __restrict__ part_ml, const int4* __restrict__ pairs,
-    _Float16* __restrict__ out, int s, int nsplit, int by, _Float16* smem, bool rev = false, int hz = 0) {
+    _Float16* __restrict__ out, int s, int nsplit, int by, _Float16* smem, bool rev = false, int hz = 0,
+    const float* __restrict__ esc = nullptr) {
   using G = XGeo<D, CH>;
   constexpr int QP = G::QP, PP = G::PP, KH = G::KH, KS = G::KS, NT = G::NT, NW = G::NW,
                 NKT = G::NKT, HPW = G::HPW;
@@ -93,6 +102,9 @@ __device__ __forceinline__ void xattn_body(
   const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
   const int t0 = s * kps, t1 = min(Te, t0 + kps);
   const _Float16* eb = enc + (int64_t)e * Te * D;
+  static_assert(!I8 || (!PF2 && !ROWLD && !SC1Q), "int8 encoder output: the one-deep fragment loads");
+  const signed char* eq = reinterpret_cast<const signed char*>(enc) + (int64_t)e * Te * D;   // (I8)
+  const float* es = I8 ? esc + (int64_t)e * Te : nullptr;
 
   // S-phase role: key tile nt (16 keys), dims half kh; the wave's Qk fragments (rows =
   // heads, zero rows >= H) stay in registers for the whole split
@@ -115,7 +127,19 @@ __device__ __forceinline__ void xattn_body(
   static_assert(!ROWLD || (D == 512 && CH == 64 && DIRECT && !PAIR && KS == CH / NW),
                 "row loads: one 1 KB key row per register slot");
   half8 ef[KS], eg[KS];  // eg: the second chunk in flight (PF2)
+  xu32x2 rq[I8 ? KS : 1];  // (I8) the chunk in flight as loaded: 8 int8 per slot and the key's scale
+  float rs = 0.f;
   auto load_to = [&](half8 (&dst)[KS], int t) __attribute__((always_inline)) {
+    if constexpr (I8) {
+      const int key = t + 16 * nt + lr;
+      const bool ok = key < t1;
+      const signed char* src = eq + (int64_t)key * D + kh * KH + 8 * lg;
+      rs = ok ? es[key] : 0.f;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        rq[ks] = ok ? *reinterpret_cast<const xu32x2*>(src + 32 * ks) : xu32x2{0u, 0u};
+      return;
+    }
     if constexpr (ROWLD) {
 #pragma unroll
       for (int i = 0; i < KS; ++i) {
@@ -157,7 +181,25 @@ __device__ __forceinline__ void xattn_body(
   auto chunk = [&](int t, half8 (&cur)[KS]) __attribute__((always_inline)) {
     // ---- S partial: rows = heads, cols = keys 16nt.., k = dims of half kh
     f32x4 accs = zero_f32x4();
-    if constexpr (ROWLD) {
+    if constexpr (I8) {
+      // E' slot by slot: float(q) * s in fp32, one rounding to fp16, into the S MFMA and its
+      // sE row — one half8 live at a time beside the 8-byte slots as loaded
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        half8 ev;
+        // (the two dwords taken as they are here: otherwise the byte extraction moves up to
+        // the loads and the chunk in flight occupies 8 registers per slot, not 2)
+        unsigned q0 = rq[ks][0], q1 = rq[ks][1];
+        asm volatile("" : "+v"(q0), "+v"(q1));
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          ev[j] = (_Float16)((float)(signed char)((j < 4 ? q0 : q1) >> (8 * (j & 3))) * rs);
+        accs = mfma16(qa[ks], ev, accs);
+        *reinterpret_cast<half8*>(sE + (16 * nt + lr) * QP + kh * KH + 32 * ks + 8 * lg) = ev;
+        // (each slot's conversion stays beside its own MFMA and LDS store)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else if constexpr (ROWLD) {
       // the wave's 8 key rows -> sE, the next chunk's rows in flight, then the S fragments
       // from sE once every wave's rows are in
 #pragma unroll

@@ -60,7 +60,7 @@ from .. import _native as nat
 from ..common import wavio
 from ..tokenizer import LANGUAGES, SOT_PREV, TASKS
 from ..whisper import (CONFIGS, WhisperEngine, check_beam_args, check_encoder_compute,
-                       check_family_features, check_history_args, resolve_model,
+                       check_family_features, check_history_args, cross_compute_mode, resolve_model,
                        resolve_suppress_tokens, shared_rows_in_place)
 from . import vad_filter as vf
 
@@ -895,11 +895,17 @@ class WhisperModel:
     fp16 weights on MFMA with fp32 accumulation in every case. With the
     default ``apply_compute_type=False`` every ``compute_type`` runs fp16 — what
     ``Transcriber`` gets, whose parity tests against the fp32 oracle depend on it.
-    ``effective_compute_type`` reports what runs: ``"float16"`` or ``"int8_float16"``."""
+    ``effective_compute_type`` reports what runs: ``"float16"`` or ``"int8_float16"``.
+
+    ``cross_compute="int8"`` (opt-in, independent of ``compute_type``) is passed to the engine:
+    every decode call quantises its encoder rows per key to int8 and the decoder's
+    cross-attention streams those (WhisperEngine); the word alignment and the
+    language detection keep the fp16 rows. ValueError for any other name but ``"float16"``."""
 
     def __init__(self, model_size: str, device: str = "auto", compute_type: str = "default",
                  *, apply_compute_type: bool = False, vad_weights: dict = None, alignment_heads=None,
-                 **_ignored):
+                 cross_compute: str = "float16", **_ignored):
+        cross_compute_mode(cross_compute)   # ValueError: unknown name
         model_size = resolve_model(model_size)   # ValueError: unknown; "turbo" -> "large-v3-turbo"
         if device not in DEVICES:
             raise ValueError(f"unsupported device {device!r}; one of {DEVICES}")
@@ -910,6 +916,8 @@ class WhisperModel:
         # alignment_heads: [(layer, head)] for word_timestamps instead of the default set (needed where
         # that set exceeds the alignment pass's 64 heads: medium.en's has 192)
         kw = {} if alignment_heads is None else {"alignment_heads": alignment_heads}
+        if cross_compute != "float16":
+            kw["cross_compute"] = cross_compute
         self.engine = WhisperEngine(CONFIGS[model_size], encoder_compute=enc_compute, **kw)
         self.stats = {"windows": 0, "needs_fallback": 0, "no_speech_skips": 0, "fallback_decodes": 0}
         # vad_filter: silero weights (default: JANUS_VAD_DIR; none: the energy stand-in); the

@@ -407,6 +407,18 @@ def encoder_compute_mode(name) -> int:
     return ENCODER_COMPUTE[name]
 
 
+# compute types of the decoder's cross-attention operand (janus.h JANUS_CROSS_COMPUTE_*)
+CROSS_COMPUTE = {"float16": 0, "int8": 1}
+CROSS_COMPUTE_NAMES = ("float16", "int8")
+
+
+def cross_compute_mode(name) -> int:
+    """"float16" / "int8" -> JANUS_CROSS_COMPUTE_*; ValueError for anything else."""
+    if not isinstance(name, str) or name not in CROSS_COMPUTE:
+        raise ValueError(f"cross_compute must be one of {sorted(CROSS_COMPUTE)}, not {name!r}")
+    return CROSS_COMPUTE[name]
+
+
 ALIGN_MAX_HEADS = 64   # alignment heads of one engine (csrc/align_plan.h kAlignMaxHeads)
 
 
@@ -451,12 +463,20 @@ class WhisperEngine:
 
     encoder_compute: "float16" (default: fp16 weights and activations on the fp16 MFMA) or
     "int8" (the encoder's QKV / out_proj / fc1 / fc2 on the i8 MFMA with row-wise symmetric
-    quantisation, CTranslate2's int8 compute type). The decoder is fp16 in
-    both."""
+    quantisation, CTranslate2's int8 compute type). The decoder's weights are
+    fp16 in both.
+
+    cross_compute: "float16" (default: the decoder's cross-attention streams the encoder
+    output it is handed) or "int8" (every decode call quantises its encoder rows per key to
+    int8 first, CTranslate2's rule for the input of the cross-attention K / V projections, and
+    the cross-attention streams those: half the bytes; include/janus.h
+    janus_whisper_set_cross_compute). align() and detect_language() read the
+    fp16 rows in both."""
 
     def __init__(self, cfg: WhisperConfig, weights: dict = None, seed: int = 0,
-                 encoder_compute: str = "float16", alignment_heads=None):
+                 encoder_compute: str = "float16", alignment_heads=None, cross_compute: str = "float16"):
         mode = encoder_compute_mode(encoder_compute)
+        cross = cross_compute_mode(cross_compute)
         check_encoder_compute(cfg, mode)
         if alignment_heads is not None:
             alignment_heads = check_alignment_heads(cfg, alignment_heads)
@@ -478,6 +498,8 @@ class WhisperEngine:
             nat.call("janus_whisper_set_tensor", self._h, name.encode(), a.ctypes.data, a.size)
         if mode != ENCODER_COMPUTE["float16"]:
             nat.call("janus_whisper_set_encoder_compute", self._h, mode)
+        if cross != CROSS_COMPUTE["float16"]:
+            nat.call("janus_whisper_set_cross_compute", self._h, cross)
         self.alignment_heads = alignment_heads or default_alignment_heads(cfg)
         if alignment_heads is not None:
             pairs = np.ascontiguousarray(np.asarray(alignment_heads, np.int32).reshape(-1, 2))
@@ -495,6 +517,19 @@ class WhisperEngine:
         between calls); the int8 weights are quantised on the first int8 encode()."""
         check_encoder_compute(self.cfg, mode)
         nat.call("janus_whisper_set_encoder_compute", self._h, encoder_compute_mode(mode))
+
+    @property
+    def cross_compute(self) -> str:
+        """The operand the next decode call's cross-attention reads: "float16" | "int8"."""
+        m = ctypes.c_int32(-1)
+        nat.call("janus_whisper_cross_compute", self._h, ctypes.addressof(m))
+        return CROSS_COMPUTE_NAMES[m.value]
+
+    def set_cross_compute(self, mode: str) -> None:
+        """Switch the cross-attention's encoder output between "float16" and "int8" (either
+        direction, between calls); "float16" again is bit-identical to never having left it."""
+        m = cross_compute_mode(mode)   # ValueError: unknown name
+        nat.call("janus_whisper_set_cross_compute", self._h, m)
 
     def set_tensor(self, name: str, arr) -> None:
         """Re-upload one parameter (janus_whisper_set_tensor); the next call re-prepares
@@ -928,10 +963,12 @@ class WhisperEngine:
         """Which path the last decode call took (janus_whisper_decode_path): a DecodePath
         of ``enc_rows`` ("own": no enc_index; "in_place": shared encoder rows read where
         they lie; "gathered": one encoder copy per decoder row) and ``persistent`` (the
-        persistent level actually run; 0 = the launch path)."""
-        er, ps = ctypes.c_int32(0), ctypes.c_int32(0)
+        persistent level actually run; 0 = the launch path) and ``cross`` (the encoder output
+        its cross-attention read: "float16" | "int8", janus_whisper_decode_cross)."""
+        er, ps, cr = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
         nat.call("janus_whisper_decode_path", self._h, ctypes.addressof(er), ctypes.addressof(ps))
-        return DecodePath(ENC_ROWS_NAMES[int(er.value)], int(ps.value))
+        nat.call("janus_whisper_decode_cross", self._h, ctypes.addressof(cr))
+        return DecodePath(ENC_ROWS_NAMES[int(er.value)], int(ps.value), CROSS_COMPUTE_NAMES[int(cr.value)])
 
     def texts(self, tokens: torch.Tensor, prompt_lens=None):
         """Host-side detokenisation of decoded rows (after each row's prompt)."""
@@ -949,6 +986,7 @@ ENC_ROWS_NAMES = ("own", "in_place", "gathered")
 class DecodePath:
     enc_rows: str      # "own" | "in_place" | "gathered"
     persistent: int    # persistent level the call ran (0: the launch path)
+    cross: str = "float16"   # "float16" | "int8": the encoder output the cross-attention read
 
 
 def shared_rows_in_place(cfg) -> bool:
