@@ -239,11 +239,14 @@ def gates(text: str, avg_logprob: float, no_speech_prob: float):
     return needs, skip
 
 
-def split_window(tk, tokens, seek, segment_size):
+def split_window(tk, tokens, seek, segment_size, time_offset=None):
     """One window's tokens -> ([(start_s, end_s, tokens)], next seek) as faster-whisper's
-    generate_segments slices them (timestamps included in the token lists)."""
+    generate_segments slices them (timestamps included in the token lists). ``time_offset``:
+    the seconds the window's times start at (None: the seek's, seek * 0.01; the batched call's
+    chunks start between frames)."""
     tb = tk.timestamp_begin
-    time_offset = seek * HOP / 16000.0
+    if time_offset is None:
+        time_offset = seek * HOP / 16000.0
     single_ending = len(tokens) >= 2 and tokens[-2] < tb <= tokens[-1]
     consecutive = [i for i in range(1, len(tokens)) if tokens[i] >= tb and tokens[i - 1] >= tb]
     segs = []
@@ -341,12 +344,13 @@ def merge_punctuations(alignment, prepended=PREPEND_PUNCTUATIONS, appended=APPEN
 
 def add_word_timestamps(tk, segments, alignment, seek, last_speech_timestamp,
                         prepend_punctuations=PREPEND_PUNCTUATIONS,
-                        append_punctuations=APPEND_PUNCTUATIONS):
+                        append_punctuations=APPEND_PUNCTUATIONS, time_offset=None):
     """faster-whisper add_word_timestamps over ONE window: ``segments`` its sub-segments as
     dicts(start, end, tokens) (times absolute), updated in place with "words" ([dict(word,
     start, end, probability)], absolute times rounded to 0.01 s) and the start / end the word
     times move; ``alignment``: find_alignment's words of the window's concatenated text
-    tokens. Returns the new last_speech_timestamp."""
+    tokens. ``time_offset``: the seconds the alignment's times start at (None: seek * 0.01).
+    Returns the new last_speech_timestamp."""
     if not segments:
         return last_speech_timestamp
     per_segment = [[t for t in seg["tokens"] if t < tk.eot] for seg in segments]
@@ -362,7 +366,8 @@ def add_word_timestamps(tk, segments, alignment, seek, last_speech_timestamp,
                 elif alignment[i - 1]["word"] in SENTENCE_END_MARKS:
                     alignment[i]["start"] = alignment[i]["end"] - max_duration
     merge_punctuations(alignment, prepend_punctuations, append_punctuations)
-    time_offset = seek * 0.01
+    if time_offset is None:
+        time_offset = seek * 0.01
     word_index = 0
     for seg, seg_tokens in zip(segments, per_segment):
         saved, words = 0, []
@@ -1093,7 +1098,16 @@ class Transcriber:
         return [' '.join(s.text.strip() for s in st.segments).strip() for st in streams]
 
 
-__all__ = ["Transcriber", "WhisperModel", "Segment", "Word", "find_alignment", "merge_punctuations",
+def __getattr__(name):
+    """BatchedInferencePipeline / generate_segments_batched live in services/batched.py (which
+    imports this module) and are exported here beside WhisperModel, resolved on first use."""
+    if name in ("BatchedInferencePipeline", "generate_segments_batched"):
+        from . import batched
+        return getattr(batched, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+__all__ = ["Transcriber", "WhisperModel", "BatchedInferencePipeline", "generate_segments_batched", "Segment", "Word", "find_alignment", "merge_punctuations",
            "add_word_timestamps", "word_seek", "window_text_tokens", "TranscriptionInfo", "read_wav_16k",
            "generate_segments", "settle_round", "advance", "gather_windows", "split_window", "compression_ratio", "gates", "nat",
            "Candidate", "candidate", "best_hypothesis", "settle", "fallback_seed", "TEMPERATURES",

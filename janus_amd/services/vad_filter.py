@@ -174,22 +174,100 @@ def speech_probabilities(audios, device, vad=None, max_chunks_per_pass: int = 0)
     the energy stand-in (janus_vad_energy, decim 1) over the zero-padded 512-sample windows —
     the contract of VoiceActivityDetector without weights."""
     import torch
+    offsets = np.zeros(len(audios) + 1, np.int64)
+    offsets[1:] = np.cumsum([len(a) for a in audios])
+    flat = np.concatenate([np.asarray(a, np.float32) for a in audios] + [np.zeros(1, np.float32)])
+    return speech_probabilities_device(torch.from_numpy(flat).to(device), offsets, vad, max_chunks_per_pass)
+
+
+def speech_probabilities_device(pcm, offsets, vad=None, max_chunks_per_pass: int = 0):
+    """speech_probabilities of utterances that already lie on the device: ``pcm`` f32 (device) =
+    the 16 kHz audio of S utterances concatenated, ``offsets`` [S + 1] (host) in samples. ONE
+    gate call; the stand-in's zero-padded windows are laid out on the device (copies of
+    ``pcm``'s ranges), so a caller that keeps the buffer uploads its audio once."""
+    import torch
 
     from .vad import _energy_prob
-    counts = [n_windows(len(a)) for a in audios]
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
     if vad is not None:
-        offsets = np.zeros(len(audios) + 1, np.int64)
-        offsets[1:] = np.cumsum([len(a) for a in audios])
-        flat = np.concatenate([np.asarray(a, np.float32) for a in audios] + [np.zeros(1, np.float32)])
-        return vad.probs_file(torch.from_numpy(flat).to(device), offsets, max_chunks_per_pass)
-    padded = np.zeros(sum(counts) * WINDOW, np.float32)
+        return vad.probs_file(pcm, offs, max_chunks_per_pass)
+    counts = [n_windows(int(n)) for n in np.diff(offs)]
+    padded = torch.zeros(sum(counts) * WINDOW, dtype=torch.float32, device=pcm.device)
     at = 0
-    for a, n in zip(audios, counts):
-        padded[at:at + len(a)] = a
+    for k, n in enumerate(counts):
+        a, b = int(offs[k]), int(offs[k + 1])
+        padded[at:at + b - a] = pcm[a:b]
         at += n * WINDOW
-    p = _energy_prob(torch.from_numpy(padded).to(device).reshape(-1, WINDOW), 1).cpu().numpy()
+    p = _energy_prob(padded.reshape(-1, WINDOW), 1).cpu().numpy()
     return [p[o - n:o] for n, o in zip(counts, np.cumsum(counts))]
 
 
+# ---------------------------------------------------------------- batched transcription
+# BatchedInferencePipeline's chunk rule (services/batched.py, DESIGN.md §5s; parity unpinned
+# like the rule above: faster-whisper is not reachable offline, so this text is the rule).
+CHUNK_LENGTH_S = 30
+BATCHED_MIN_SILENCE_MS = 160   # min_silence_duration_ms of the batched call without vad_parameters
+
+
+def merge_segments(speeches, chunk_length_s: float = CHUNK_LENGTH_S):
+    """[(start, end, [(s, e), ...])] in samples: consecutive ``speeches`` ([(s, e)], samples,
+    in order) merged into chunks of at most ``chunk_length_s`` seconds. A speech whose end
+    lies more than the limit after the open chunk's start closes that chunk (when it holds
+    anything) and opens the next at its own start, so a single speech longer than the limit
+    is a chunk of its own. A chunk is the contiguous span [start, end): the pauses between
+    its speeches stay inside. No speeches: no chunks."""
+    speeches = [(int(s), int(e)) for s, e in speeches]
+    if not speeches:
+        return []
+    limit = SAMPLE_RATE * chunk_length_s
+    out = []
+    curr_start, curr_end, inside = speeches[0][0], 0, []
+    for s, e in speeches:
+        if e - curr_start > limit and curr_end - curr_start > 0:
+            out.append((curr_start, curr_end, inside))
+            curr_start, inside = s, []
+        curr_end = e
+        inside.append((s, e))
+    out.append((curr_start, curr_end, inside))
+    return out
+
+
+def batched_vad_options(vad_parameters=None, chunk_length_s: float = CHUNK_LENGTH_S) -> VadOptions:
+    """The VadOptions of the batched call: None -> the defaults with min_silence_duration_ms
+    160; a dict / VadOptions keeps its fields; ``max_speech_duration_s`` is ``chunk_length_s``
+    in every case, so no speech outgrows a chunk."""
+    if vad_parameters is None:
+        return VadOptions(min_silence_duration_ms=BATCHED_MIN_SILENCE_MS, max_speech_duration_s=chunk_length_s)
+    return dataclasses.replace(as_vad_options(vad_parameters), max_speech_duration_s=chunk_length_s)
+
+
+def clip_chunks(clip_timestamps, n_samples: int):
+    """merge_segments' form for ``clip_timestamps``: (start_s, end_s) pairs or {"start", "end"}
+    dicts in SECONDS, taken as given (sample = round(16000 t), cut to the audio); ValueError
+    for a clip that ends before it starts."""
+    out = []
+    for c in clip_timestamps:
+        a, b = (c["start"], c["end"]) if isinstance(c, dict) else c
+        s, e = int(round(float(a) * SAMPLE_RATE)), int(round(float(b) * SAMPLE_RATE))
+        if s < 0 or e < s:
+            raise ValueError(f"clip_timestamps: ({a!r}, {b!r}) is no clip (0 <= start <= end, seconds)")
+        s, e = min(s, n_samples), min(e, n_samples)
+        out.append((s, e, [(s, e)]))
+    return out
+
+
+NO_CLIPS = "No clip timestamps found. Set 'vad_filter' to True or provide 'clip_timestamps'."
+
+
+def whole_file_chunk(n_samples: int, chunk_length_s: float = CHUNK_LENGTH_S):
+    """Neither the filter nor clips: audio of at most one chunk is the chunk [0, n);
+    longer audio is faster-whisper's RuntimeError."""
+    if n_samples > SAMPLE_RATE * chunk_length_s:
+        raise RuntimeError(NO_CLIPS)
+    return [(0, int(n_samples), [(0, int(n_samples))])]
+
+
 __all__ = ["VadOptions", "as_vad_options", "get_speech_timestamps", "collect_chunks", "SpeechTimestampsMap",
-           "restore_speech_timestamps", "speech_probabilities", "n_windows", "WINDOW", "SAMPLE_RATE"]
+           "restore_speech_timestamps", "speech_probabilities", "speech_probabilities_device", "n_windows",
+           "merge_segments", "batched_vad_options", "clip_chunks", "whole_file_chunk", "CHUNK_LENGTH_S",
+           "BATCHED_MIN_SILENCE_MS", "WINDOW", "SAMPLE_RATE"]
