@@ -147,6 +147,55 @@ int janus_vad_run(janus_vad* v, const float* pcm, int n_streams, int n_chunks, i
 int janus_vad_probs(janus_vad* v, const float* pcm, const int64_t* offsets, int n_streams,
                     int max_chunks_per_pass, float* prob, void* stream);
 
+/* ---------------------------------------------------------- resampling --- */
+/*
+ * Band-limited resampling of f32 audio from sr_in to sr_out (resample.hip): the step
+ * faster-whisper's decode_audio takes through PyAV / libswresample before the model sees a
+ * file. That filter cannot be pinned offline (parity unpinned against PyAV / libswresample),
+ * so the rule is stated here and tests/resample_ref.py evaluates it in float64.
+ *
+ * g = gcd(sr_in, sr_out), L = sr_out / g, M = sr_in / g.
+ *   Filter: s = min(1, L / M), Z = 32, beta = 10, W = Z / s (half width in input samples),
+ *     phi(u) = s sinc(s u) I0(beta sqrt(1 - (u / W)^2)) / I0(beta) for |u| < W, else 0,
+ *     sinc(v) = sin(pi v) / (pi v).
+ *   Output length: n_out = ceil(n_in L / M).
+ *   Output n: p = n mod L, i = n div L, c = (p M) div L, frac = (p M mod L) / L;
+ *     taps h_p[k] = phi(frac - k) over the integers k with |frac - k| < W, normalised in
+ *     float64 so that sum_k h_p[k] = 1 and then rounded once to float32;
+ *     y[n] = sum_k h_p[k] x[i M + c + k], x = 0 outside [0, n_in).
+ *   Output n sits at input time n M / L: no delay, each phase's taps symmetric about it.
+ * The kernel sums each output as one k-ordered fmaf chain in float32.
+ *
+ * Limits: both rates in 4000 .. 384000 and L <= 640 (44101 -> 16000 is refused); the message
+ * names both rates. sr_in == sr_out is a copy (L = M = T = 1, the tap 1).
+ *
+ * janus_resample_plan: the host plan alone, no device. L, M, T (taps of the widest phase)
+ * and, where the pointers are given, first [L] (output i L + p starts at x[i M + first[p]],
+ * first[p] = c + the least k) and taps f32 [L][T] (phase p's row, zero past its last tap);
+ * the capacities are in elements and are checked.
+ *
+ * A resampler holds the plan of one pair, its tap matrix on the device and a grow-only
+ * staging buffer. janus_resampler_info: L, M, T, out_tile (the output samples one block of
+ * the kernel computes for a clip) and front (the zeros the staging buffer holds in front of
+ * each clip, >= ceil(W) + 1); any pointer may be null.
+ *
+ * janus_resample_f32: pcm [device] f32 = n_clips clips of rate sr_in concatenated, offsets
+ * [host] [n_clips + 1] in samples, as janus_vad_probs takes them; out [device] f32,
+ * out_offsets [host] [n_clips + 1] with out_offsets[c + 1] - out_offsets[c] = ceil(n_c L / M)
+ * (checked). Clip c is copied behind `front` zeros into the staging buffer, zeros follow up
+ * to the end of its last tile, and the kernel reads nothing else: no sample of one clip
+ * reaches another clip's output and a clip's bits do not depend on what it is batched with.
+ * n_clips = 0, or clips that are all empty, launch nothing.
+ */
+typedef struct janus_resampler janus_resampler;
+int janus_resample_plan(int sr_in, int sr_out, int* L, int* M, int* T, int32_t* first,
+                        int64_t first_capacity, float* taps, int64_t taps_capacity);
+int janus_resampler_create(int sr_in, int sr_out, janus_resampler** out);
+int janus_resampler_destroy(janus_resampler* r);
+int janus_resampler_info(const janus_resampler* r, int* L, int* M, int* T, int* out_tile, int* front);
+int janus_resample_f32(janus_resampler* r, const float* pcm, const int64_t* offsets, int n_clips,
+                       float* out, const int64_t* out_offsets, void* stream);
+
 /* -------------------------------------------------------- packet codec --- */
 enum {
   JANUS_VAL_NIL = 0,

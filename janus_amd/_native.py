@@ -60,6 +60,11 @@ SIGNATURES = {
     "janus_vad_set_tensor": [_P, ctypes.c_char_p, _P, _I64],
     "janus_vad_run": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P],
     "janus_vad_probs": [_P, _P, _P, _I32, _I32, _P, _P],
+    "janus_resample_plan": [_I32, _I32, _P, _P, _P, _P, _I64, _P, _I64],
+    "janus_resampler_create": [_I32, _I32, _P],
+    "janus_resampler_destroy": [_P],
+    "janus_resampler_info": [_P, _P, _P, _P, _P, _P],
+    "janus_resample_f32": [_P, _P, _P, _I32, _P, _P, _P],
     "janus_prosody_analyze": [_P, _P, _P, _I32, _I64, _I32, _I32, _F32, _F32, _P, _P, _P, _P,
                               _P, _P, _P],
     "janus_prosody_analyze_ex": [_P, _P, _P, _I32, _I64, _I32, _I32, _F32, _F32, _P, _P, _P, _P,

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "decode_shapes.h"  // kSkinnyMaxRows
+#include "resample_plan.h"  // kResampleBlockRows
 
 namespace janus {
 
@@ -267,6 +268,17 @@ void silero_vad_launch(const float* pcm, int n_streams, int n_chunks, int chunk_
 void silero_vad_file_launch(const float* pcm, const int64_t* offsets_dev, const int64_t* chunk_off_dev,
                             int n_streams, int64_t max_chunks, int pass_chunks, const VadWeights& W,
                             float* pre, float* hc_state, float* prob, hipStream_t s);
+
+// ------------------------------------------------------------------ resampler
+// Band-limited resampling (resample.hip) of n_clips clips of one rate pair. meta_dev int64
+// [5][n_clips]: offset in pcm | n_in | index of sample 0 in stage | offset in out | n_out.
+// stage must be zero wherever no sample is copied and hold, for every clip, -kmin floats in
+// front of sample 0 and (rows16 - 1) Mg + kend behind it (rows16 = the clip's n_out / Lg
+// rows rounded up to 16; kmin, kend, tile_meta [n_ct][3] and table: ResampleTiles; the block
+// geometry kResampleWaves / kResampleRowTiles / kResampleBlockRows: resample_plan.h).
+void resample_launch(const float* pcm, const int64_t* meta_dev, int n_clips, int64_t max_n_in,
+                     int64_t max_n_out, float* stage, const int32_t* tile_meta, const float* table,
+                     int Lg, int Mg, int n_ct, float* out, hipStream_t s);
 
 // ------------------------------------------------------------------ mel
 void mel_launch(const float* pcm, const int64_t* offsets, int B, const float* basis,

@@ -377,9 +377,7 @@ class BatchedInferencePipeline:
         if hallucination_silence_threshold is not None:
             raise NotImplementedError("hallucination_silence_threshold is not supported")
         m._check_language(language, task)
-        if isinstance(audio, str):
-            audio = tr.read_wav_16k(audio)
-        audio = np.ascontiguousarray(audio, dtype=np.float32)
+        audio = m._load_audio(audio)
         use_vad = bool(vad_filter) and not clip_timestamps
         res = generate_segments_batched(
             m.engine, [audio], batch_size=batch_size, max_length=max_length, max_new_tokens=max_new_tokens,

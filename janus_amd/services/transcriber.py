@@ -51,12 +51,14 @@ over all its frames), from which each window takes the content frames
 (``features[:, seek:seek + segment_size]`` + ``pad_or_trim``).
 """
 import dataclasses
+import os
 import zlib
 
 import numpy as np
 import torch
 
 from .. import _native as nat
+from ..audio import decode_audio
 from ..common import wavio
 from ..tokenizer import LANGUAGES, SOT_PREV, TASKS
 from ..whisper import (CONFIGS, WhisperEngine, check_beam_args, check_encoder_compute,
@@ -202,6 +204,15 @@ class TranscriptionInfo:
 
 
 read_wav_16k = wavio.read_wav_16k  # 16-bit PCM WAV -> f32 @ 16 kHz
+
+# how WhisperModel brings a file to 16 kHz: the reference's rule, or decode_audio's filter
+AUDIO_RESAMPLE = ("reference", "bandlimited")
+
+
+def audio_resample_mode(name: str) -> str:
+    if name not in AUDIO_RESAMPLE:
+        raise ValueError(f"unsupported audio_resample {name!r}; one of {AUDIO_RESAMPLE}")
+    return name
 
 # faster-whisper's device / compute_type vocabulary (WhisperModel(model_size, device=...,
 # compute_type=...)); every value names the SAME GPU engine here (see WhisperModel)
@@ -905,12 +916,19 @@ class WhisperModel:
     ``cross_compute="int8"`` (opt-in, independent of ``compute_type``) is passed to the engine:
     every decode call quantises its encoder rows per key to int8 and the decoder's
     cross-attention streams those (WhisperEngine); the word alignment and the
-    language detection keep the fp16 rows. ValueError for any other name but ``"float16"``."""
+    language detection keep the fp16 rows. ValueError for any other name but ``"float16"``.
+
+    ``audio_resample`` says how a file (a path, a PathLike, an open binary file or bytes)
+    becomes 16 kHz audio: ``"reference"`` (the default) is ``read_wav_16k``, the reference's
+    ``[::3]`` at 48 kHz and linear interpolation elsewhere; ``"bandlimited"`` is
+    ``janus_amd.audio.decode_audio``. ValueError for any other name. Arrays
+    are taken as 16 kHz audio either way."""
 
     def __init__(self, model_size: str, device: str = "auto", compute_type: str = "default",
                  *, apply_compute_type: bool = False, vad_weights: dict = None, alignment_heads=None,
-                 cross_compute: str = "float16", **_ignored):
+                 cross_compute: str = "float16", audio_resample: str = "reference", **_ignored):
         cross_compute_mode(cross_compute)   # ValueError: unknown name
+        self._audio_resample = audio_resample_mode(audio_resample)   # ValueError: unknown name
         model_size = resolve_model(model_size)   # ValueError: unknown; "turbo" -> "large-v3-turbo"
         if device not in DEVICES:
             raise ValueError(f"unsupported device {device!r}; one of {DEVICES}")
@@ -938,6 +956,21 @@ class WhisperModel:
             if w is not None:
                 self._vad_gate = SileroGate(w)
         return self._vad_gate
+
+    @property
+    def audio_resample(self) -> str:
+        return getattr(self, "_audio_resample", "reference")
+
+    def _load_audio(self, audio):
+        """What transcribe, detect_language and BatchedInferencePipeline.transcribe make of
+        ``audio``: a path, a PathLike, an open binary file or bytes is read and brought to
+        16 kHz under ``audio_resample``; anything else is an array of 16 kHz samples."""
+        if isinstance(audio, (str, os.PathLike, bytes, bytearray, memoryview)) or hasattr(audio, "read"):
+            if self.audio_resample == "bandlimited":
+                audio = decode_audio(audio)
+            else:
+                audio = read_wav_16k(os.fspath(audio) if isinstance(audio, os.PathLike) else audio)
+        return np.ascontiguousarray(audio, dtype=np.float32)
 
     @property
     def is_multilingual(self) -> bool:
@@ -972,9 +1005,7 @@ class WhisperModel:
             raise ValueError(f"detect_language: {self.model_size} is English-only")
         if language_detection_segments < 1:
             raise ValueError("language_detection_segments must be >= 1")
-        if isinstance(audio, str):
-            audio = read_wav_16k(audio)
-        audio = np.ascontiguousarray(audio, dtype=np.float32)
+        audio = self._load_audio(audio)
         eng, st = self.engine, _Stream(audio)
         if st.content_frames <= 0:
             raise ValueError("detect_language: empty audio")
@@ -1023,9 +1054,7 @@ class WhisperModel:
         if hallucination_silence_threshold is not None:
             raise NotImplementedError("hallucination_silence_threshold is not supported")
         self._check_language(language, task)
-        if isinstance(audio, str):
-            audio = read_wav_16k(audio)
-        audio = np.ascontiguousarray(audio, dtype=np.float32)
+        audio = self._load_audio(audio)
         temps = (float(temperature),) if np.isscalar(temperature) else tuple(temperature)
         vad_options = vf.as_vad_options(vad_parameters) if vad_filter else None
         st = generate_segments(self.engine, [audio], max_length=max_length, temperatures=temps,
@@ -1107,7 +1136,7 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["Transcriber", "WhisperModel", "BatchedInferencePipeline", "generate_segments_batched", "Segment", "Word", "find_alignment", "merge_punctuations",
+__all__ = ["Transcriber", "WhisperModel", "decode_audio", "BatchedInferencePipeline", "generate_segments_batched", "Segment", "Word", "find_alignment", "merge_punctuations",
            "add_word_timestamps", "word_seek", "window_text_tokens", "TranscriptionInfo", "read_wav_16k",
            "generate_segments", "settle_round", "advance", "gather_windows", "split_window", "compression_ratio", "gates", "nat",
            "Candidate", "candidate", "best_hypothesis", "settle", "fallback_seed", "TEMPERATURES",
