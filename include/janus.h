@@ -320,7 +320,8 @@ int janus_whisper_encode(janus_whisper* w, const uint16_t* mel, int batch, uint1
  * quantised per output row from the fp32 parameters on first use (and again after a
  * janus_whisper_set_tensor), activations per row on the fly, int32 accumulation on the i8
  * MFMA. The conv stem, attention, LayerNorms, residual stream and the whole decoder are the
- * same in both modes. The mode may be switched between calls, in either direction.
+ * same in both modes (the decoder's weights have a switch of their own,
+ * janus_whisper_set_decoder_compute). The mode may be switched between calls, in either direction.
  */
 #define JANUS_ENC_COMPUTE_F16 0
 #define JANUS_ENC_COMPUTE_INT8 1
@@ -361,6 +362,56 @@ int janus_whisper_cross_compute(janus_whisper* w, int32_t* mode);
 /* The JANUS_CROSS_COMPUTE_* the last decode call on this context ran with (the lane
  * janus_whisper_decode_path reports; JANUS_CROSS_COMPUTE_F16 before any call). */
 int janus_whisper_decode_cross(janus_whisper* w, int32_t* mode);
+/*
+ * Compute type of the decoder's weights. F16 (the default): every decoder linear layer and
+ * the vocabulary projection multiply the prepared fp16 weights. INT8: W8A16, weights int8,
+ * activations fp16 as in F16.
+ *  1. Quantisation. Per output row n of each prepared fp16 weight matrix W16 [N][K] (the fp16
+ *     copy the F16 path multiplies): amax = max_k |W16[n][k]|,
+ *     q[n][k] = clamp(rint(float(W16[n][k]) * (127 / amax)), -127, 127), s[n] = amax / 127; a
+ *     zero row gives q = 0, s = 1. float32 arithmetic with IEEE division (no reciprocal
+ *     approximation): numpy float32 reproduces q and s exactly; the rule of
+ *     janus_whisper_set_cross_compute. Matrices, per decoder layer (JANUS_DEC_W_*): the fused
+ *     self-attention QKV weight, the self-attention output projection, the absorbed
+ *     cross-attention query weight (quantised from its fp16 absorbed form), the cross-attention
+ *     value and output projections, fc1, fc2; and the token embedding as the vocabulary
+ *     projection's table. The copies are made on the first decode call in the mode and again
+ *     after janus_whisper_set_tensor.
+ *  2. Product. A layer output is y[m][n] = s[n] * sum_k a[m][k] * q[n][k] + bias[n]: a fp16, q
+ *     converted exactly to fp16, the products on the fp16 MFMA with fp32 accumulation, scale
+ *     and bias applied in fp32, then the F16 path's epilogue (fp16 store, GELU, the QKV cache
+ *     write, the fp32 residual add). A logit is s[v] * sum_k a[k] * q[v][k]; the rule filter,
+ *     statistics, Gumbel keys and history rules run on it unchanged.
+ *  3. Unchanged whatever the mode: the embedding lookup (it reads the fp16 table), the
+ *     LayerNorms, both attentions, the residual stream, janus_whisper_align,
+ *     janus_whisper_detect_language and the encoder. The fp16 weights stay resident: the int8
+ *     copies are extra memory, not a saving.
+ * Under INT8 every layer runs unfused (a LayerNorm launch in front of each projection, the
+ * cross-attention's split merge and the value projection as two launches) and a `persistent`
+ * request runs the launch path (janus_whisper_decode_path reports 0). Honoured by
+ * janus_whisper_decode_greedy(_ex), _sample_ex, _sample_rows_ex and the test entry
+ * janus_whisper_decode_hidden, shared encoder rows, staggered rows and the history rules
+ * included, and composed with JANUS_CROSS_COMPUTE_INT8. REJECTED with INT8 (non-zero status,
+ * janus_last_error, nothing enqueued): janus_whisper_decode_beam_ex, JANUS_DEC_PATH_NO_XABSORB,
+ * JANUS_DEC_PATH_XGROUP and a call of more than 512 rows. The mode may be switched between
+ * calls, in either direction; F16 again is bit-identical to a context that never left it.
+ * janus_whisper_decode_weights tells which weights the last decode call multiplied.
+ */
+#define JANUS_DEC_COMPUTE_F16 0
+#define JANUS_DEC_COMPUTE_INT8 1
+int janus_whisper_set_decoder_compute(janus_whisper* w, int mode);
+int janus_whisper_decoder_compute(janus_whisper* w, int32_t* mode);
+/* The JANUS_DEC_COMPUTE_* the last decode call on this context ran with (the lane
+ * janus_whisper_decode_path reports; JANUS_DEC_COMPUTE_F16 before any call). */
+int janus_whisper_decode_weights(janus_whisper* w, int32_t* mode);
+/* the quantised matrices of a decoder layer (janus_whisper_decoder_weight_i8, janus_kernels.h) */
+#define JANUS_DEC_W_QKV 0     /* [3 d][d] */
+#define JANUS_DEC_W_O 1       /* [d][d] */
+#define JANUS_DEC_W_XQK 2     /* [H d][d], the absorbed cross-attention query weight */
+#define JANUS_DEC_W_XV 3      /* [d][d] */
+#define JANUS_DEC_W_XO 4      /* [d][d] */
+#define JANUS_DEC_W_FC1 5     /* [4 d][d] */
+#define JANUS_DEC_W_FC2 6     /* [d][4 d] */
 
 typedef struct {
   const int32_t* prompt;   /* [host] initial tokens, e.g. {<|startoftranscript|>} for *.en */

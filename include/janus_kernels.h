@@ -256,6 +256,34 @@ int janus_logits_partial_hist_f16(const uint16_t* A, const uint16_t* W, int K, i
                                   const uint8_t* smask, const int32_t* row_rules, int max_blocks,
                                   float inv_temp, const uint32_t* seeds, int pos, void* parts,
                                   const uint32_t* hist, float repetition_penalty, void* stream);
+/* Int8 decoder weights (rule at janus_whisper_set_decoder_compute, janus.h).
+ * janus_quant_weight_rows_i8: x fp16 [M][K] (row stride ldx) -> q int8 [M][K] (row stride
+ * ldq), scale [M]; any K % 8 == 0.
+ * janus_gemm_w8_f16: janus_gemm_f16 with W replaced by q int8 [N][K] (row stride ldw) and
+ * scale [N]; M <= 512 rows on the skinny kernel, epi also 4 (the QKV cache epilogue is not
+ * reachable here: 0 .. 3); a_group_cols > 0: the grouped (block-diagonal) product.
+ * janus_logits_partial_w8_f16 / janus_logits_partial_hist_w8_f16: janus_logits_partial_f16 /
+ * janus_logits_partial_hist_f16 with W replaced by the int8 table q [V][K] and scale [V]. */
+int janus_quant_weight_rows_i8(const uint16_t* x, int64_t ldx, int8_t* q, int64_t ldq, float* scale, int M,
+                               int K, void* stream);
+int janus_gemm_w8_f16(int epi, const uint16_t* A, int64_t lda, const int8_t* q, const float* scale,
+                      int64_t ldw, const float* bias, void* C, int64_t ldc, const float* R, int64_t ldr,
+                      int M, int N, int K, int a_group_cols, void* stream);
+int janus_logits_partial_w8_f16(const uint16_t* A, const int8_t* q, const float* scale, int K, int V, int batch,
+                                int eot, int suppress_blank, int blank, int ts_begin, int no_timestamps,
+                                int max_initial_ts, int target, const uint8_t* smask, const int32_t* row_rules,
+                                int max_blocks, float inv_temp, const uint32_t* seeds, int pos, void* parts,
+                                void* stream);
+int janus_logits_partial_hist_w8_f16(const uint16_t* A, const int8_t* q, const float* scale, int K, int V,
+                                     int batch, int eot, int suppress_blank, int blank, int ts_begin,
+                                     int no_timestamps, int max_initial_ts, int target, const uint8_t* smask,
+                                     const int32_t* row_rules, int max_blocks, float inv_temp,
+                                     const uint32_t* seeds, int pos, void* parts, const uint32_t* hist,
+                                     float repetition_penalty, void* stream);
+/* One quantised matrix of a prepared context, read back to the host: layer 0 .. dec_layers - 1
+ * and which = JANUS_DEC_W_*, or layer -1 (which ignored): the vocabulary table. q_out [host]
+ * int8 [N][K], s_out [host] float [N]. Prepares the int8 copies if the context has none. */
+int janus_whisper_decoder_weight_i8(janus_whisper* w, int layer, int which, int8_t* q_out, float* s_out);
 int janus_beam_logits_topk_f16(const uint16_t* A, const uint16_t* W, int K, int V, int batch,
                                int eot, int suppress_blank, int blank, int ts_begin,
                                int no_timestamps, int max_initial_ts, const uint8_t* smask,
@@ -302,6 +330,15 @@ int janus_decode_plan_describe_cross(const janus_whisper_config* cfg, const janu
                                      int beam_size, const int32_t* stand, int n_stand, int stand_maxlen,
                                      int cross_compute, char* text, int text_cap, int64_t* key,
                                      int key_cap, int32_t* n_key);
+/* The same with the decoder weights' compute type as well (JANUS_DEC_COMPUTE_*,
+ * janus_whisper_set_decoder_compute); janus_decode_plan_describe_cross is this entry at
+ * JANUS_DEC_COMPUTE_F16. */
+int janus_decode_plan_describe_modes(const janus_whisper_config* cfg, const janus_decode_options* opt,
+                                     const janus_decode_rows* rows, int batch, int cus, int resident,
+                                     int multi_lane, float temperature, const float* temperatures,
+                                     int beam_size, const int32_t* stand, int n_stand, int stand_maxlen,
+                                     int cross_compute, int dec_compute, char* text, int text_cap,
+                                     int64_t* key, int key_cap, int32_t* n_key);
 
 /*
  * Test-only view of the decoder's residual stream: a teacher-forced run of the decode call's

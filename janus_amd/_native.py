@@ -86,6 +86,9 @@ SIGNATURES = {
     "janus_whisper_set_cross_compute": [_P, _I32],
     "janus_whisper_cross_compute": [_P, _P],
     "janus_whisper_decode_cross": [_P, _P],
+    "janus_whisper_set_decoder_compute": [_P, _I32],
+    "janus_whisper_decoder_compute": [_P, _P],
+    "janus_whisper_decode_weights": [_P, _P],
     "janus_whisper_decode_greedy": [_P, _P, _I32, _P, _P, _P, _P, _P],
     "janus_whisper_decode_greedy_ex": [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
     "janus_whisper_decode_sample_ex": [_P, _P, _I32, _P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _P],
@@ -118,6 +121,14 @@ SIGNATURES = {
     "janus_wave_xor_f32": [_P, _P, _I32, _P],
     "janus_quant_rows_i8": [_P, _I64, _P, _I64, _P, _I32, _I32, _P],
     "janus_layernorm_quant_i8": [_P, _P, _P, _P, _P, _I32, _I32, _F32, _P],
+    # int8 decoder weights: the quantiser, the W8A16 skinny GEMM and vocabulary projection, read-back
+    "janus_quant_weight_rows_i8": [_P, _I64, _P, _I64, _P, _I32, _I32, _P],
+    "janus_gemm_w8_f16": [_I32, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P],
+    "janus_logits_partial_w8_f16": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P,
+                                    _I32, _F32, _P, _I32, _P, _P],
+    "janus_logits_partial_hist_w8_f16": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P,
+                                         _P, _I32, _F32, _P, _I32, _P, _P, _F32, _P],
+    "janus_whisper_decoder_weight_i8": [_P, _I32, _I32, _P, _P],
     "janus_gemm_i8": [_I32, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _P],
     "janus_resid_ln_f16": [_P, _I64, _P, _I64, _P, _P, _P, _P, _F32, _P, _I32, _I32, _I32, _P],
     "janus_gemm_ln_f16": [_I32, _P, _I64, _P, _P, _F32, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _P],
@@ -158,6 +169,8 @@ SIGNATURES = {
                                    _P, _I32, _P, _I32, _P],
     "janus_decode_plan_describe_cross": [_P, _P, _P, _I32, _I32, _I32, _I32, _F32, _P, _I32, _P, _I32, _I32,
                                          _I32, _P, _I32, _P, _I32, _P],
+    "janus_decode_plan_describe_modes": [_P, _P, _P, _I32, _I32, _I32, _I32, _F32, _P, _I32, _P, _I32, _I32,
+                                         _I32, _I32, _P, _I32, _P, _I32, _P],
     # test-only view of the decoder's residual stream (teacher-forced decode machinery)
     "janus_whisper_decode_hidden": [_P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, _P],
 }

@@ -351,13 +351,20 @@ struct DecodeStep : LaneBuffers {
     p.kc = kcp; p.vc = vcp; p.pos = pos; p.n_ctx = NC; p.qkv_d = d;
     return p;
   }
+  // the layer's matrix JANUS_DEC_W_* (which) as the product reads it: the fp16 weights, or under
+  // the int8 decoder weights their int8 copy and row scales (GemmArgs::Wq)
+  GemmArgs wsel(GemmArgs g, const DecLayer& L, int which) const {
+    g.W = L.w16(which).as<_Float16>();
+    if (P.dec_i8) { g.W = nullptr; g.Wq = L.q8[which].as<int8_t>(); g.wscale = L.s8[which].as<float>(); }
+    return g;
+  }
   GemmArgs with_ln(GemmArgs g, const float* lg, const float* lb, bool on) const {
     if (on) { g.lnin_x = x; g.lnin_ldx = d; g.lnin_g = lg; g.lnin_b = lb; g.lnin_eps = 1e-5f; }
     return g;
   }
-  void resid(const _Float16* A, int K, const DevMem& W, const float* bias, const float* ng,
+  void resid(const _Float16* A, int K, const DecLayer& L, int which, const float* bias, const float* ng,
              const float* nb) const {
-    GemmArgs g = dgargs(A, K, W.as<_Float16>(), K, bias, x, d, B, d, K, x, d);
+    GemmArgs g = wsel(dgargs(A, K, nullptr, K, bias, x, d, B, d, K, x, d), L, which);
     if (fused_ln) g.ln_part = lnp;
     if (ln_fuse) { g.ln_g = ng; g.ln_b = nb; g.ln_out = a; g.ln_cnt = lncnt; }
     gemm_launch(EPI_RESID_F32, g, s);
@@ -422,8 +429,8 @@ struct DecodeStep : LaneBuffers {
       if (!ln_fuse && !lnp1 && !(embed_ln && l == 0))
         layernorm_launch(x, L.ln1g, L.ln1b, a, B, d, 1e-5f, s);
       if (B <= kSkinnyMaxRows) {
-        GemmArgs g = with_ln(dgargs(a, d, L.wqkv.as<_Float16>(), d, L.bqkv.as<float>(), qkv, 3 * d, B, 3 * d, d),
-                             L.ln1g, L.ln1b, lnp1);
+        GemmArgs g = with_ln(wsel(dgargs(a, d, nullptr, d, L.bqkv.as<float>(), qkv, 3 * d, B, 3 * d, d), L,
+                                  JANUS_DEC_W_QKV), L.ln1g, L.ln1b, lnp1);
         g.kc = kc; g.vc = vc; g.pos = pos; g.n_ctx = NC; g.qkv_d = d;
         g.roff = roff;
         gemm_launch(EPI_QKV, g, s);
@@ -470,8 +477,8 @@ struct DecodeStep : LaneBuffers {
                                             xqk, hd, hd, nullptr, nullptr, pos), s);
     } else {
       if (!ln_fuse && !lnp2 && !rln2) layernorm_launch(x, L.ln2g, L.ln2b, a, B, d, 1e-5f, s);
-      gemm_launch(EPI_F16, with_ln(dgargs(a, d, L.wqk.as<_Float16>(), d, L.bqk.as<float>(), xqk, hd, B, hd, d),
-                                   L.ln2g, L.ln2b, lnp2), s);
+      gemm_launch(EPI_F16, with_ln(wsel(dgargs(a, d, nullptr, d, L.bqk.as<float>(), xqk, hd, B, hd, d), L,
+                                        JANUS_DEC_W_XQK), L.ln2g, L.ln2b, lnp2), s);
     }
     // o_h = c_h Wv_h^T + bv_h (block-diagonal over heads), then x += o Wo^T + bo; the
     // split merge and the value projection in one launch (cvp) where supported
@@ -496,12 +503,12 @@ struct DecodeStep : LaneBuffers {
       xattn_combine_vproj_launch(xpc, xpml, xsplit, B, H, d,
                                  L.wv_c.as<_Float16>(), L.bv_c, o, d, s);
     } else {
-      GemmArgs gv = dgargs(xc, hd, L.wv_c.as<_Float16>(), d, L.bv_c, o, d, B, d, d);
+      GemmArgs gv = wsel(dgargs(xc, hd, nullptr, d, L.bv_c, o, d, B, d, d), L, JANUS_DEC_W_XV);
       gv.a_group_cols = 64;
       gemm_launch(EPI_F16, gv, s);
     }
     if (rln3) resid_ln(o, L.wo_c, L.bo_c, L.ln3g, L.ln3b);
-    else resid(o, d, L.wo_c, L.bo_c, L.ln3g, L.ln3b);
+    else resid(o, d, L, JANUS_DEC_W_XO, L.bo_c, L.ln3g, L.ln3b);
   }
 
   // LN2, the query projection and the cross-attention over the per-layer projected K / V
@@ -520,7 +527,7 @@ struct DecodeStep : LaneBuffers {
     decode_attention_split_launch(q2, d, ck, cv, (int64_t)Te * d, d, Te, o, d, B, H, scale, part_o,
                                   part_ml, s);
     if (rln3) resid_ln(o, L.wo_c, L.bo_c, L.ln3g, L.ln3b);
-    else resid(o, d, L.wo_c, L.bo_c, L.ln3g, L.ln3b);
+    else resid(o, d, L, JANUS_DEC_W_XO, L.bo_c, L.ln3g, L.ln3b);
   }
 
   // LN3, fc1 + GELU, fc2 + residual
@@ -531,11 +538,11 @@ struct DecodeStep : LaneBuffers {
                                                  4 * d, nullptr, nullptr, pos), s);
     } else {
       if (!ln_fuse && !lnp3 && !rln3) layernorm_launch(x, L.ln3g, L.ln3b, a, B, d, 1e-5f, s);
-      gemm_launch(EPI_GELU_F16, with_ln(dgargs(a, d, L.w1.as<_Float16>(), d, L.b1, f, 4 * d, B, 4 * d, d),
-                                        L.ln3g, L.ln3b, lnp3), s);
+      gemm_launch(EPI_GELU_F16, with_ln(wsel(dgargs(a, d, nullptr, d, L.b1, f, 4 * d, B, 4 * d, d), L,
+                                             JANUS_DEC_W_FC1), L.ln3g, L.ln3b, lnp3), s);
     }
     // next LayerNorm: the following layer's LN1, or the decoder's final LN
-    resid(f, 4 * d, L.w2, L.b2, l + 1 < nl ? w->dec[l + 1].ln1g : fin_g,
+    resid(f, 4 * d, L, JANUS_DEC_W_FC2, L.b2, l + 1 < nl ? w->dec[l + 1].ln1g : fin_g,
           l + 1 < nl ? w->dec[l + 1].ln1b : fin_b);
   }
 
@@ -551,7 +558,8 @@ struct DecodeStep : LaneBuffers {
                           lnp_fin ? x : nullptr, d, fin_g, fin_b, P.lg_cap,
                           P.sampling ? seed : nullptr, pos,
                           P.row_temps ? itemp : nullptr,
-                          P.beam_k ? btop : nullptr, hist, P.rep_pen);
+                          P.beam_k ? btop : nullptr, hist, P.rep_pen,
+                          P.dec_i8 ? w->tokq.as<int8_t>() : nullptr, P.dec_i8 ? w->toks.as<float>() : nullptr);
     if (P.beam_k) {
       beam_step_launch(parts, btop, nblk, R, rules,
                        tokens, maxlen, pos, done, sum_lp, n_tokens, prompt,
@@ -596,7 +604,7 @@ struct DecodeStep : LaneBuffers {
         continue;
       }
       if (rln2) resid_ln(o, L.wo, L.bo, L.ln2g, L.ln2b);
-      else resid(o, d, L.wo, L.bo, L.ln2g, L.ln2b);
+      else resid(o, d, L, JANUS_DEC_W_O, L.bo, L.ln2g, L.ln2b);
       if (P.xabs) absorbed_cross_attention(l, pos);
       else projected_cross_attention(l, pos);
       mlp(l, pos);
@@ -713,7 +721,7 @@ static void decode_lane(janus_whisper* w, DecLane& Z, const DecodeCall& call, in
   lane_check(Z);   // the previous non-polling call's flag first
   const DecodePlan P = plan_decode(w->cfg, *call.opt, call.rows, call.smp, call.beam, B, stream_cu_count(s),
                                    latch != nullptr, LaneStand{&Z.stand, Z.stand_maxlen},
-                                   SegDevice{dec_seg_grid, dec_seg_resident}, w->cross_compute);
+                                   SegDevice{dec_seg_grid, dec_seg_resident}, w->cross_compute, w->dec_compute);
   // until this call completes, nothing may be continued (a failed call leaves stand empty)
   Z.stand.clear();
   const LaneBuffers b = ensure_buffers(w, Z, P, call.opt->n_suppress, s);
@@ -727,6 +735,7 @@ static void decode_lane(janus_whisper* w, DecLane& Z, const DecodeCall& call, in
   Z.last_enc_rows = P.enc_rows;
   Z.last_persist = P.persist;
   Z.last_cross = P.cross_i8 ? JANUS_CROSS_COMPUTE_INT8 : JANUS_CROSS_COMPUTE_F16;
+  Z.last_weights = P.dec_i8 ? JANUS_DEC_COMPUTE_INT8 : JANUS_DEC_COMPUTE_F16;
   run_positions(Z, P, b, step, s);
   finish(Z, P, b, call, bst, s);
 }
@@ -770,7 +779,7 @@ static void hidden_lane(janus_whisper* w, DecLane& Z, const DecodeCall& call, in
   lane_check(Z);
   const DecodePlan P = plan_decode(w->cfg, *call.opt, call.rows, nullptr, nullptr, B, stream_cu_count(s), false,
                                    LaneStand{&Z.stand, Z.stand_maxlen}, SegDevice{dec_seg_grid, dec_seg_resident},
-                                   w->cross_compute);
+                                   w->cross_compute, w->dec_compute);
   JANUS_CHECK(P.steps <= x_positions, "decode_hidden: x_out holds fewer positions than the call runs");
   const std::string desc = P.describe();
   JANUS_CHECK(text && (int64_t)desc.size() < text_cap, "decode_hidden: plan_text too small");
@@ -808,6 +817,7 @@ static void hidden_lane(janus_whisper* w, DecLane& Z, const DecodeCall& call, in
   Z.last_enc_rows = P.enc_rows;
   Z.last_persist = P.persist;
   Z.last_cross = P.cross_i8 ? JANUS_CROSS_COMPUTE_INT8 : JANUS_CROSS_COMPUTE_F16;
+  Z.last_weights = P.dec_i8 ? JANUS_DEC_COMPUTE_INT8 : JANUS_DEC_COMPUTE_F16;
   Z.stand.assign(B, 0);
   for (int r = 0; r < B; ++r) Z.stand[r] = (P.stagger() ? P.roff[r] : 0) + P.steps;
   Z.stand_maxlen = P.maxlen;
@@ -832,6 +842,7 @@ extern "C" int janus_whisper_decode_hidden(janus_whisper* w, const uint16_t* enc
     std::lock_guard<std::mutex> lk(w->mu);
     hipStream_t s = (hipStream_t)stream;
     prepare(w, s);
+    if (w->dec_compute == JANUS_DEC_COMPUTE_INT8) prepare_dec_i8(w, s);
     janus_decode_options o = *opt;
     o.max_length = n + 1;   // every position is inside the prompt: nothing is sampled
     while ((int)w->lanes.size() <= o.state_slot) w->lanes.emplace_back(new DecLane());
@@ -1021,6 +1032,15 @@ extern "C" int janus_whisper_decode_cross(janus_whisper* w, int32_t* mode) {
   });
 }
 
+extern "C" int janus_whisper_decode_weights(janus_whisper* w, int32_t* mode) {
+  return guarded([&] {
+    JANUS_CHECK(w && mode, "null argument");
+    std::lock_guard<std::mutex> lk(w->mu);
+    const int sl = w->last_slot < (int)w->lanes.size() ? w->last_slot : 0;
+    *mode = w->lanes.empty() ? JANUS_DEC_COMPUTE_F16 : w->lanes[sl]->last_weights;
+  });
+}
+
 static int decode_entry(janus_whisper* w, const uint16_t* enc, int batch,
                         const janus_decode_options* opt, const janus_decode_rows* rows,
                         int32_t* tokens, int32_t* n_tokens, float* sum_logprob,
@@ -1032,6 +1052,7 @@ static int decode_entry(janus_whisper* w, const uint16_t* enc, int batch,
     std::lock_guard<std::mutex> lk(w->mu);
     hipStream_t s = (hipStream_t)stream;
     prepare(w, s);
+    if (w->dec_compute == JANUS_DEC_COMPUTE_INT8 && !beam) prepare_dec_i8(w, s);
     const _Float16* e = reinterpret_cast<const _Float16*>(enc);
     // lanes: janus_decode_options.lanes (default 1). Two half-batch lanes measured slower at B = 64
     // (428.7 vs 419.6 ms per bench step): the skinny projections are weight-stream

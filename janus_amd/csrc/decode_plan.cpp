@@ -232,13 +232,16 @@ static void plan_paths(DecodePlan& P, const janus_whisper_config& c, const janus
   // written by the producer of each residual row, normalised on load by the consumer).
   // Opt-in: with the 16-wave skinny GEMM the separate LayerNorm launch measured faster
   // (637.7 vs 660.8 ms per bench step) — the consumer ingests A as fp32.
-  const bool fused_ln = P.fused_ln = B <= 64 && path(JANUS_DEC_PATH_FUSED_LN);
+  // (the int8 decoder weights, i8 below, have no LayerNorm-on-load, resid_ln or merge + value
+  // projection form: every layer runs unfused, as the models above d_model 512 run it)
+  const bool i8 = P.dec_i8;
+  const bool fused_ln = P.fused_ln = B <= 64 && !i8 && path(JANUS_DEC_PATH_FUSED_LN);
   // JANUS_DEC_PATH_LN_FUSE (opt-in, B <= 64): LayerNorm handed off inside the producing kernel —
   // the residual GEMM's last block normalises the new rows (GemmArgs::ln_out, sc1 stores
   // + arrival counter), the embedding kernel normalises its row; no LayerNorm launches.
   // Measured slower than the separate launches (616.8 vs 536.5 ms per bench step): the
   // write-through stores and the serial tail cost more than the launch they save.
-  const bool ln_fuse = P.ln_fuse = B <= 64 && !fused_ln && d <= 512 && path(JANUS_DEC_PATH_LN_FUSE);
+  const bool ln_fuse = P.ln_fuse = B <= 64 && !i8 && !fused_ln && d <= 512 && path(JANUS_DEC_PATH_LN_FUSE);
   // LayerNorm in the consuming projection's prologue (GemmArgs::lnin_x: each block
   // normalises its rows of x into an fp16 LDS tile; the vocabulary projection the final
   // LayerNorm) instead of a LayerNorm launch.
@@ -253,27 +256,27 @@ static void plan_paths(DecodePlan& P, const janus_whisper_config& c, const janus
   // staggered 2 x 64 rows) every LayerNorm is its own launch: decoder side 230-234 ms with
   // mask 0 against 235-241 (9), 245-249 (13), 265-269 (15) on one box
   // (profiles/r04_decoder_knobs.json): each prologue normalises its block's rows again.
-  P.ln_pro_mask = (B <= kSkinnyMaxRows && d <= 512 && !fused_ln && !ln_fuse)
+  P.ln_pro_mask = (B <= kSkinnyMaxRows && d <= 512 && !i8 && !fused_ln && !ln_fuse)
                       ? (path(JANUS_DEC_PATH_LN_PROLOGUE) ? (int)((pf >> 12) & 15u)
                                                           : (B <= 64 ? 9 : 0))
                       : 0;
   // the embedding kernel owns whole rows (one block per utterance): it also writes the
   // first layer's LayerNorm of its row, one launch fewer per position
   // (JANUS_NO_EMBED_LN restores the separate launch)
-  P.embed_ln = !fused_ln && !ln_fuse && d <= 512 && !path(JANUS_DEC_PATH_NO_EMBED_LN);
+  P.embed_ln = !i8 && !fused_ln && !ln_fuse && d <= 512 && !path(JANUS_DEC_PATH_NO_EMBED_LN);
   // Opt-in (JANUS_DEC_PATH_RESID_LN): the attention output projections and the LayerNorm after
   // them (LN2 / LN3) in one launch (resid_ln_kernel: 16 rows per block over all d columns,
   // bit-identical to the residual GEMM + LayerNorm pair). Measured 72 ms per step SLOWER
   // on the decoder side (361 vs 289 ms): at B = 64 only 4 blocks stream the 0.5 MB weight
   // each, at ~25 GB/s per CU (≈ 24 µs per launch against 5.6 + 5.0 µs for the pair).
-  const bool rln = P.rln = B <= 64 && !fused_ln && !ln_fuse && resid_ln_supported(d, d) &&
+  const bool rln = P.rln = B <= 64 && !i8 && !fused_ln && !ln_fuse && resid_ln_supported(d, d) &&
                            path(JANUS_DEC_PATH_RESID_LN);
   // the split merge fused into the per-head value projection (one launch) up to 64 rows;
   // above (the staggered 2 x 64 rows) the merge in the cross-attention's last split block
   // and a block-diagonal skinny projection measured faster (decoder side -1.5 / -2.9 ms
   // per step on two boxes, profiles/r04_decoder_knobs.json); bit-identical either way
   // (xattn_combine_vproj_kernel; JANUS_DEC_PATH_NO_CVP / _CVP force either form)
-  P.cvp = xattn_cvp_supported(d, H) && xsplit <= 16 && !path(JANUS_DEC_PATH_NO_CVP) &&
+  P.cvp = !i8 && xattn_cvp_supported(d, H) && xsplit <= 16 && !path(JANUS_DEC_PATH_NO_CVP) &&
           (B <= 64 || P.ngroups() > 0 || path(JANUS_DEC_PATH_CVP));
   // the selection at pos and the embedding at pos + 1 in one launch (select_embed_kernel,
   // bit-identical; JANUS_DEC_PATH_NO_SEL_EMBED restores the two launches): a step from the first
@@ -296,9 +299,10 @@ static void plan_paths(DecodePlan& P, const janus_whisper_config& c, const janus
   // the same CUs, keeps the launch path)
   // (beam search runs the launch path: a persistent request falls back, as at d_model 768;
   // so does a call with history rules)
-  // (the int8 cross-attention likewise: the persistent levels' one-split forms are not built for it)
+  // (the int8 cross-attention likewise: the persistent levels' one-split forms are not built for it;
+  // and the int8 decoder weights: the segments multiply the fp16 weights)
   const int seg_grid = P.seg_grid =
-      opt.persistent && !multi_lane && !P.beam_k && !P.hist() && !P.cross_i8
+      opt.persistent && !multi_lane && !P.beam_k && !P.hist() && !P.cross_i8 && !i8
           ? seg.grid(B, cus, path(JANUS_DEC_PATH_SEG_2CU)) : 0;
   const bool persist = seg_grid > 0 && dec_seg_supported(d, H, B, cus) && seg.resident(seg_grid, cus) &&
                        xabs && !P.shared() && !fused_ln && !ln_fuse && !rln && P.ngroups() == 0 && P.npairs() == 0;
@@ -325,9 +329,26 @@ static void plan_paths(DecodePlan& P, const janus_whisper_config& c, const janus
 DecodePlan plan_decode(const janus_whisper_config& cfg, const janus_decode_options& opt,
                        const janus_decode_rows* rows, const DecodeSampling* smp, const BeamMode* beam,
                        int B, int cus, bool multi_lane, const LaneStand& stand, const SegDevice& seg,
-                       int cross_compute) {
+                       int cross_compute, int dec_compute) {
   DecodePlan P;
   P.B = B;
+  // int8 decoder weights (janus_whisper_set_decoder_compute): greedy and sampled calls on the
+  // absorbed launch path
+  JANUS_CHECK(dec_compute == JANUS_DEC_COMPUTE_F16 || dec_compute == JANUS_DEC_COMPUTE_INT8,
+              "decode: decoder_compute must be 0 (float16) or 1 (int8)");
+  if ((P.dec_i8 = dec_compute == JANUS_DEC_COMPUTE_INT8)) {
+    const uint32_t pf = opt.path_flags;
+    JANUS_CHECK(!beam, "decode: beam search with decoder_compute int8: the beam partials of the vocabulary "
+                       "projection read the fp16 table only");
+    JANUS_CHECK(!(pf & JANUS_DEC_PATH_NO_XABSORB),
+                "decode: JANUS_DEC_PATH_NO_XABSORB with decoder_compute int8: the per-layer cross K / V and "
+                "query projections have no int8 weights");
+    JANUS_CHECK(!(pf & JANUS_DEC_PATH_XGROUP),
+                "decode: JANUS_DEC_PATH_XGROUP with decoder_compute int8: GROUP blocks need the fused merge + "
+                "value projection, which reads the fp16 weights only");
+    JANUS_CHECK(xattn_supported(cfg.d_model, cfg.n_heads) && B <= kSkinnyMaxRows,
+                "decode: decoder_compute int8 needs the absorbed cross-attention (d_model 384 .. 1280, <= 512 rows)");
+  }
   // int8 cross-attention (janus_whisper_set_cross_compute): the absorbed launch path's one-row,
   // PAIR and one-split forms only
   JANUS_CHECK(cross_compute == JANUS_CROSS_COMPUTE_F16 || cross_compute == JANUS_CROSS_COMPUTE_INT8,
@@ -364,6 +385,7 @@ std::string DecodePlan::describe() const {
               [&](const char* n, auto v) { o << "call." << n << '=' << +v << '\n'; });
   if (hist()) o << "repetition_penalty=" << rep_pen << "\nno_repeat_ngram_size=" << ngram << '\n';
   if (cross_i8) o << "cross_int8=1\n";
+  if (dec_i8) o << "dec_int8=1\n";
   o << "pairs=";
   for (size_t i = 0; i < pairs.size(); ++i)
     o << (i ? "," : "") << pairs[i].b0 << ',' << pairs[i].b1 << ',' << pairs[i].e;

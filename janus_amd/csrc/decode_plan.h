@@ -61,6 +61,8 @@ inline int64_t key_word(bool v) { return v; }
 
 // the graph key's word of a call with the int8 cross-attention ("xi8" above any 32-bit field)
 constexpr int64_t kCrossI8KeyWord = (int64_t)0x786938 << 32;
+// likewise of a call with the int8 decoder weights ("wi8")
+constexpr int64_t kDecI8KeyWord = (int64_t)0x776938 << 32;
 
 struct DecodePlan {
   // ---- shape and counts
@@ -94,6 +96,9 @@ struct DecodePlan {
   int ngram = 0;
   // the cross-attention over the call's encoder rows quantised to int8 (janus_whisper_set_cross_compute)
   bool cross_i8 = false;
+  // every decoder linear layer and the vocabulary projection on the int8 weights
+  // (janus_whisper_set_decoder_compute): the unfused launch path
+  bool dec_i8 = false;
   // ---- host arrays to upload
   std::vector<XPair> pairs;
   std::vector<int> groups;  // [ngroups][8] = {e, row_0 .. row_6 (-1: none)}
@@ -139,6 +144,7 @@ struct DecodePlan {
     if (hist()) { key.push_back(key_word(rep_pen)); key.push_back(key_word(ngram)); }
     // likewise the int8 cross-attention: one tagged word, only when set
     if (cross_i8) key.push_back(kCrossI8KeyWord);
+    if (dec_i8) key.push_back(kDecI8KeyWord);
   }
   bool operator==(const DecodePlan& o) const {
     std::vector<int64_t> a, b;
@@ -149,17 +155,19 @@ struct DecodePlan {
   // name=value lines (janus_decode_plan_describe): the step fields, the call fields as
   // call.name, then pairs= and groups= as integer lists; repetition_penalty= and
   // no_repeat_ngram_size= lines in front of pairs= only on a call that sets one of them, and
-  // cross_int8=1 after them only on a call with the int8 cross-attention
+  // cross_int8=1 after them only on a call with the int8 cross-attention, dec_int8=1 after that
+  // only on a call with the int8 decoder weights
   std::string describe() const;
 };
 
 // Checks the call's arguments (every rejection a janus::Error, before anything is enqueued)
 // and decides its path. cus: the CUs of the caller's stream (stream_cu_count);
 // multi_lane: the call is one lane of several running concurrently. cross_compute: the
-// context's JANUS_CROSS_COMPUTE_* (janus_whisper_set_cross_compute).
+// context's JANUS_CROSS_COMPUTE_* (janus_whisper_set_cross_compute); dec_compute: its
+// JANUS_DEC_COMPUTE_* (janus_whisper_set_decoder_compute).
 DecodePlan plan_decode(const janus_whisper_config& cfg, const janus_decode_options& opt,
                        const janus_decode_rows* rows, const DecodeSampling* smp, const BeamMode* beam,
                        int B, int cus, bool multi_lane, const LaneStand& stand, const SegDevice& seg,
-                       int cross_compute = JANUS_CROSS_COMPUTE_F16);
+                       int cross_compute = JANUS_CROSS_COMPUTE_F16, int dec_compute = JANUS_DEC_COMPUTE_F16);
 
 }  // namespace janus

@@ -93,7 +93,10 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
                            const float* ln_b = nullptr, int max_blocks = 256,
                            const uint32_t* seeds = nullptr, int pos = 0,
                            const float* row_inv_temp = nullptr, BeamTop* tops = nullptr,
-                           const uint32_t* hist = nullptr, float rep_pen = 1.f);
+                           const uint32_t* hist = nullptr, float rep_pen = 1.f,
+                           const int8_t* Wq = nullptr, const float* wscale = nullptr);
+// Wq / wscale (nullable; greedy, sampling and the history rules, no beam partials, no lnx): the
+// int8 table [V][K] and its row scales replace W: logit = wscale[v] * sum_k A[k] * fp16(Wq[v][k])
 // hist (nullable; greedy and sampling, no beam partials): the rows' history words
 // (history_rules_launch) — a penalised column's logit is scaled by rep_pen (> 0) before the
 // filter, a banned column fails it; the raw statistics stay unpenalised

@@ -411,14 +411,21 @@ int logits_partial_blocks(int V, int K, int max_blocks) {
 // before the filter, a banned column fails it like a suppressed token. The raw statistics
 // (t_v, m_raw, s_raw) stay on the unpenalised logits; a lane whose word is 0 runs the
 // sibling's epilogue unchanged (the plain tile's shortcut included).
-template <int NKS, int NB, bool SAMPLE, bool BEAM = false, int MT = 4, bool HIST = false>  // K / 32
+// W8 (int8 decoder weights, janus_whisper_set_decoder_compute): W is the int8 table [V][K] and
+// wscale its row scales. The tile in flight is NKS x 8 bytes per lane (80 VGPRs at K = 1280
+// where the fp16 tile holds 160), converted exactly to fp16 (w8_half8) in front of each MFMA;
+// the column's scale arrives with the tile's mask bytes and multiplies the fp32 sums where
+// the patch is written: logit = wscale[v] * sum_k a[k] * q[v][k]. Everything after the patch
+// is the fp16 form's. No BEAM form.
+template <int NKS, int NB, bool SAMPLE, bool BEAM = false, int MT = 4, bool HIST = false, bool W8 = false>  // K / 32
 __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel(
     const _Float16* __restrict__ A, int lda, const _Float16* __restrict__ W, int V, int B,
     DecodeRules R, const uint8_t* __restrict__ smask, const RowRules* __restrict__ rules,
     LogitPart* __restrict__ parts, int ntiles, const float* __restrict__ lnx, int ldx,
     const float* __restrict__ ln_g, const float* __restrict__ ln_b, int rot,
     const uint32_t* __restrict__ seeds, int pos, const float* __restrict__ rinv,
-    BeamTop* __restrict__ tops, const uint32_t* __restrict__ hist, float rep_pen) {
+    BeamTop* __restrict__ tops, const uint32_t* __restrict__ hist, float rep_pen,
+    const float* __restrict__ wscale) {
   extern __shared__ __attribute__((aligned(16))) _Float16 lg_smem[];
   dec_wave_prio();
   // row group blockIdx.y: rows [RG y, RG y + RG) of the call (one launch for every group:
@@ -426,6 +433,7 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
   constexpr int RG = 16 * MT;
   static_assert(!BEAM || MT == 4, "the beam merge is laid out for 64-row groups");
   static_assert(!(HIST && BEAM), "beam search takes no history rules");
+  static_assert(!(W8 && BEAM), "the beam partials read the fp16 table only");
   {
     const int r0 = (int)blockIdx.y * RG;
     A += (int64_t)r0 * lda;
@@ -447,7 +455,9 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
   const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
   // the first tile's weights and suppress-mask bytes are issued before A is staged (they
   // do not depend on it); later tiles' loads are issued before the previous epilogue
-  half8 bw[NB][NKS];
+  half8 bw[NB][W8 ? 1 : NKS];
+  uint2 bq[NB][W8 ? NKS : 1];   // W8: the tile's int8 weights
+  float wsc[NB];                // W8: the scale of column lane & 15 of the tile
   uint4 sm16[NB];
   uint32_t hw[NB];   // HIST: the history word of row = lane for the tile (one coalesced load)
   // logical tile t -> physical tile (t + rot) mod ntiles (see logits_partial_launch)
@@ -455,9 +465,16 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
 #define LG_LOAD(BUF, TILE)                                                                    \
   do {                                                                                        \
     const int bcol_ = min(phys(TILE) * 16 + (lane & 15), V - 1);                              \
-    const _Float16* wrow_ = W + (int64_t)bcol_ * K + 8 * (lane >> 4);                         \
-    _Pragma("unroll") for (int ks = 0; ks < NKS; ++ks)                                        \
-      bw[BUF][ks] = *reinterpret_cast<const half8*>(wrow_ + 32 * ks);                         \
+    if constexpr (W8) {                                                                       \
+      const int8_t* qrow_ = reinterpret_cast<const int8_t*>(W) + (int64_t)bcol_ * K + 8 * (lane >> 4); \
+      _Pragma("unroll") for (int ks = 0; ks < NKS; ++ks)                                      \
+        bq[BUF][ks] = *reinterpret_cast<const uint2*>(qrow_ + 32 * ks);                       \
+      wsc[BUF] = wscale[bcol_];                                                               \
+    } else {                                                                                  \
+      const _Float16* wrow_ = W + (int64_t)bcol_ * K + 8 * (lane >> 4);                       \
+      _Pragma("unroll") for (int ks = 0; ks < NKS; ++ks)                                      \
+        bw[BUF][ks] = *reinterpret_cast<const half8*>(wrow_ + 32 * ks);                       \
+    }                                                                                         \
     /* 16 mask bytes per tile (the mask buffer is padded to a multiple of 16) */             \
     sm16[BUF] = *reinterpret_cast<const uint4*>(smask + phys(TILE) * 16);                     \
     if constexpr (HIST) hw[BUF] = hist[(int64_t)phys(TILE) * RG + (RG < 64 ? min(lane, RG - 1) : lane)]; \
@@ -562,9 +579,21 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
       // keep the reads above the MFMAs (the scheduler otherwise sinks each read to just
       // before its MFMA to save registers, re-serialising the loop)
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (W8) {
+        const half8 bh = w8_half8(bq[u][ks]);
 #pragma unroll
-      for (int m = 0; m < MT; ++m) acc[m] = mfma16(af[ks & 1][m], bw[u][ks], acc[m]);
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16(af[ks & 1][m], bh, acc[m]);
+      } else {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) acc[m] = mfma16(af[ks & 1][m], bw[u][ks], acc[m]);
+      }
       __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (W8) {
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[m][r] *= wsc[u];
     }
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -778,13 +807,25 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
 }
 #undef LG_LOAD
 
+// the int8-table forms of logits_partial_kernel by K (one function type: same parameters)
+template <bool SAMPLE, bool HIST>
+static auto lg_w8_kernel(int K) {
+  return K == 384   ? logits_partial_kernel<12, 1, SAMPLE, false, 4, HIST, true>
+         : K == 512 ? logits_partial_kernel<16, 1, SAMPLE, false, 4, HIST, true>
+         : K == 768 ? logits_partial_kernel<24, 1, SAMPLE, false, 4, HIST, true>
+         : K == 1024 ? logits_partial_kernel<32, 1, SAMPLE, false, kLgMt1024, HIST, true>
+                     : logits_partial_kernel<40, 1, SAMPLE, false, 2, HIST, true>;
+}
+
 void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K, int V, int B,
                            const DecodeRules& R, const uint8_t* smask, const RowRules* rules,
                            LogitPart* parts, hipStream_t s, const float* lnx, int ldx,
                            const float* ln_g, const float* ln_b, int max_blocks,
                            const uint32_t* seeds, int pos, const float* row_inv_temp, BeamTop* tops,
-                           const uint32_t* hist, float rep_pen) {
+                           const uint32_t* hist, float rep_pen, const int8_t* Wq, const float* wscale) {
   JANUS_CHECK(!tops || !(R.inv_temp > 0.f), "logits: the beam partials are greedy only");
+  JANUS_CHECK(!Wq || (wscale && !tops && !lnx && ((uintptr_t)Wq & 7) == 0),
+              "logits: the int8 table needs its row scales and has no beam partials and no LayerNorm prologue");
   JANUS_CHECK(!hist || (!tops && rep_pen > 0.f), "logits: history rules need a penalty > 0 and no beam partials");
   JANUS_CHECK(K == 384 || K == 512 || K == 768 || K == 1024 || K == 1280,
               "logits: K (d_model) must be 384, 512, 768, 1024 or 1280");
@@ -814,8 +855,15 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
     if (k1280) kern = sample ? logits_partial_kernel<40, 1, true, false, 2, true> : logits_partial_kernel<40, 1, false, false, 2, true>;
     if (k1024) kern = sample ? logits_partial_kernel<32, 1, true, false, kLgMt1024, true> : logits_partial_kernel<32, 1, false, false, kLgMt1024, true>;
   }
-  static bool attr[23] = {};
-  const int ai = k1024 ? 19 + (int)sample + (hist ? 2 : 0)
+  int ai8 = -1;
+  if (Wq) {   // the int8 table's forms: greedy / sampling, with and without the history rules
+    W = reinterpret_cast<const _Float16*>(Wq);
+    kern = hist ? (sample ? lg_w8_kernel<true, true>(K) : lg_w8_kernel<false, true>(K))
+                : (sample ? lg_w8_kernel<true, false>(K) : lg_w8_kernel<false, false>(K));
+    ai8 = 23 + 4 * (K == 384 ? 0 : K == 512 ? 1 : K == 768 ? 2 : K == 1024 ? 3 : 4) + 2 * (int)sample + (hist ? 1 : 0);
+  }
+  static bool attr[23 + 20] = {};
+  const int ai = ai8 >= 0 ? ai8 : k1024 ? 19 + (int)sample + (hist ? 2 : 0)
                  : hist ? 11 + (K == 384 ? 0 : K == 512 ? 1 : K == 768 ? 2 : 3) + (sample ? 4 : 0)
                       : k1280 ? 9 + (int)sample : (K == 384 ? 0 : K == 512 ? 1 : 2) + (tops ? 6 : sample ? 3 : 0);
   if (!attr[ai]) {
@@ -843,7 +891,7 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
   // 64 (K = 1024: 48, K = 1280: 32) rows per row group (blockIdx.y), every group in one launch
   kern<<<dim3(grid, (B + rg - 1) / rg), nw * 64, lds, s>>>(A, lda, W, V, B, R, smask, rules, parts, ntiles, lnx, ldx,
                                                       ln_g, ln_b, rot, seeds, pos,
-                                                      sample ? row_inv_temp : nullptr, tops, hist, rep_pen);
+                                                      sample ? row_inv_temp : nullptr, tops, hist, rep_pen, wscale);
   JANUS_LAUNCH_CHECK();
 }
 

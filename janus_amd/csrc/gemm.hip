@@ -204,6 +204,7 @@ struct SkinnyArgs {
   const float* ln_g; const float* ln_b; float ln_eps; _Float16* ln_out; int* ln_cnt;
   const float* lnin_g; const float* lnin_b;  // AM_LNX: A = LayerNorm(x) computed in-block
   const int32_t* roff;  // EPI_QKV: per-row position offsets (row r's cache row pos + roff[r])
+  const int8_t* Wq; const float* wscale;  // W8: int8 weights [N][K] (row stride ldw) and their row scales
 };
 
 // A operand modes: fp16 from global memory; LayerNorm-on-load from producer pieces
@@ -218,8 +219,13 @@ constexpr int kSkWaves = 16;
 // K1: K <= 16 waves x 32, one k-step per wave: G = 1 keeps the all-rows form (MTB = 4)
 // under 64 VGPRs, two 16-wave blocks per CU (the 4096-wide absorbed query projection's 256
 // blocks in one round on a 128-CU partition instead of two: 91 VGPRs admitted one).
-template <int EPI, int AM, int MTB, bool K1 = false>
+// W8 (AM_F16 only; GemmArgs::Wq): the weights are int8 with one fp32 scale per output column.
+// A lane loads 8 bytes per k-step where the fp16 form loads 16 and converts them exactly to
+// fp16 in registers (w8_half8) in front of the same MFMA; the column's scale arrives with the
+// bias at kernel entry and y = scale * sum + (bias + residual) in fp32, then the epilogue.
+template <int EPI, int AM, int MTB, bool K1 = false, bool W8 = false>
 __global__ __launch_bounds__(1024) void gemm_skinny_kernel(SkinnyArgs p) {
+  static_assert(!W8 || AM == AM_F16, "int8 weights: plain fp16 A only");
   constexpr bool LNA = AM == AM_LNA, LNX = AM == AM_LNX;
   // k-steps in flight per wave (128-VGPR budget at 1024 threads; the LayerNorm modes run
   // K <= 512, one k-step per wave)
@@ -234,6 +240,7 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(SkinnyArgs p) {
   const int kbeg = w * kq, kend = min(K, kbeg + kq);
   const int bcol = col0 + (lane & 15);
   const _Float16* wrow = p.W + (int64_t)min(bcol, N - 1) * p.ldw;
+  const int8_t* qrow = p.Wq + (int64_t)min(bcol, N - 1) * p.ldw;   // (W8)
   const int lr = lane & 15, kc8 = 8 * (lane >> 4);
   const _Float16* Ab = p.A;
   if constexpr (AM == AM_F16) {
@@ -246,8 +253,11 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(SkinnyArgs p) {
   const bool eok = elr < 16 * MTB && erow < M && ecol < N;
   float e_add = (p.bias && eok) ? p.bias[ecol] : 0.0f;
   if constexpr (EPI == EPI_RESID_F32) e_add += eok ? p.R[(int64_t)erow * p.ldr + ecol] : 0.0f;
+  float e_scale = 0.0f;
+  if constexpr (W8) e_scale = eok ? p.wscale[ecol] : 0.0f;
 
-  half8 bw[G];
+  half8 bw[W8 ? 1 : G];
+  uint2 bq[W8 ? G : 1];
   half8 ah[LNA ? 1 : G][MTB];
   float4 ax[LNA ? G : 1][4][2];
   auto load = [&](int k0) {
@@ -255,7 +265,10 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(SkinnyArgs p) {
     for (int g = 0; g < G; ++g) {
       const int kk = k0 + 32 * g + kc8;
       const bool ok = kk < kend;
-      bw[g] = (ok && bcol < N) ? *reinterpret_cast<const half8*>(wrow + kk) : zero_half8();
+      if constexpr (W8)
+        bq[g] = (ok && bcol < N) ? *reinterpret_cast<const uint2*>(qrow + kk) : make_uint2(0u, 0u);
+      else
+        bw[g] = (ok && bcol < N) ? *reinterpret_cast<const half8*>(wrow + kk) : zero_half8();
 #pragma unroll
       for (int m = 0; m < MTB; ++m) {
         const int r = r0 + m * 16 + lr;
@@ -358,8 +371,14 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(SkinnyArgs p) {
 #pragma unroll
         for (int m = 0; m < MTB; ++m) af[m] = ah[g][m];
       }
+      if constexpr (W8) {
+        const half8 bh = w8_half8(bq[g]);
 #pragma unroll
-      for (int m = 0; m < MTB; ++m) acc[m] = mfma16(af[m], bw[g], acc[m]);
+        for (int m = 0; m < MTB; ++m) acc[m] = mfma16(af[m], bh, acc[m]);
+      } else {
+#pragma unroll
+        for (int m = 0; m < MTB; ++m) acc[m] = mfma16(af[m], bw[g], acc[m]);
+      }
     }
     if (k0 + 32 * G < kend) load(k0 + 32 * G);
   }
@@ -380,7 +399,14 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(SkinnyArgs p) {
   }
   __syncthreads();
   float v = e_add;
-  if (elr < 16 * MTB) {
+  if constexpr (W8) {
+    float sum = 0.0f;
+    if (elr < 16 * MTB) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sum += red[i][elr][ec];
+    }
+    v = sum * e_scale + e_add;
+  } else if (elr < 16 * MTB) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) v += red[i][elr][ec];
   }
@@ -523,11 +549,11 @@ __global__ __launch_bounds__(1024) void gemm_skinny2_kernel(SkinnyArgs p) {
   }
 }
 
-template <int AM, int EPI, int MTB>
+template <int AM, int EPI, int MTB, bool W8 = false>
 static void skinny_go(const SkinnyArgs& p, dim3 grid, hipStream_t s) {
-  auto kern = gemm_skinny_kernel<EPI, AM, MTB>;
+  auto kern = gemm_skinny_kernel<EPI, AM, MTB, false, W8>;
   if constexpr (AM == AM_F16 && MTB == 4) {
-    if (p.K <= kSkWaves * 32) kern = gemm_skinny_kernel<EPI, AM, MTB, true>;
+    if (p.K <= kSkWaves * 32) kern = gemm_skinny_kernel<EPI, AM, MTB, true, W8>;
   }
   size_t lds = 0;
   if constexpr (AM == AM_LNX) {
@@ -542,29 +568,30 @@ static void skinny_go(const SkinnyArgs& p, dim3 grid, hipStream_t s) {
   kern<<<grid, 1024, lds, s>>>(p);
 }
 
-template <int AM, int MTB>
+template <int AM, int MTB, bool W8 = false>
 static void launch_skinny_m(int epi, const SkinnyArgs& p, hipStream_t s) {
   const dim3 grid((p.N + 15) / 16, (p.M + 16 * MTB - 1) / (16 * MTB));
   switch (epi) {
-    case EPI_F16: skinny_go<AM, EPI_F16, MTB>(p, grid, s); break;
-    case EPI_GELU_F16: skinny_go<AM, EPI_GELU_F16, MTB>(p, grid, s); break;
-    case EPI_QKV: skinny_go<AM, EPI_QKV, MTB>(p, grid, s); break;
+    case EPI_F16: skinny_go<AM, EPI_F16, MTB, W8>(p, grid, s); break;
+    case EPI_GELU_F16: skinny_go<AM, EPI_GELU_F16, MTB, W8>(p, grid, s); break;
+    case EPI_QKV: skinny_go<AM, EPI_QKV, MTB, W8>(p, grid, s); break;
     case EPI_RESID_F32:
-      if constexpr (AM == AM_F16) { skinny_go<AM, EPI_RESID_F32, MTB>(p, grid, s); break; }
+      if constexpr (AM == AM_F16) { skinny_go<AM, EPI_RESID_F32, MTB, W8>(p, grid, s); break; }
       else throw Error("skinny LN gemm: bad epilogue");
     case EPI_F32:
-      if constexpr (AM == AM_F16) { skinny_go<AM, EPI_F32, MTB>(p, grid, s); break; }
+      if constexpr (AM == AM_F16) { skinny_go<AM, EPI_F32, MTB, W8>(p, grid, s); break; }
       else throw Error("skinny LN gemm: bad epilogue");
     default: throw Error("bad gemm epilogue");
   }
   JANUS_LAUNCH_CHECK();
 }
 
-template <int AM>
+template <int AM, bool W8 = false>
 static void launch_skinny_t(int epi, const SkinnyArgs& p, hipStream_t s) {
   // plain fp16 outputs wider than 2048 columns (more 16-column tiles than a 128-CU
   // partition holds in one round) at K <= 512: 32 columns per block
-  if constexpr (AM == AM_F16 || AM == AM_LNX) {
+  // (int8 weights: the 16-column forms only)
+  if constexpr ((AM == AM_F16 || AM == AM_LNX) && !W8) {
     if (epi == EPI_F16 && p.N > 2048 && p.K <= kSkWaves * 32 && p.a_group_cols == 0 && p.M <= 64) {
       if constexpr (AM == AM_LNX) {
         auto kern = gemm_skinny2_kernel<true>;
@@ -585,8 +612,8 @@ static void launch_skinny_t(int epi, const SkinnyArgs& p, hipStream_t s) {
   // narrow outputs (N <= msplit_n, default 2048: <= 128 column tiles) split the rows over
   // 16-row blocks as well, so 4x as many CUs share the latency-bound product
   constexpr int kMsplitN = 2048;
-  if (p.N <= (p.msplit_n > 0 ? p.msplit_n : kMsplitN)) { launch_skinny_m<AM, 1>(epi, p, s); return; }
-  launch_skinny_m<AM, 4>(epi, p, s);
+  if (p.N <= (p.msplit_n > 0 ? p.msplit_n : kMsplitN)) { launch_skinny_m<AM, 1, W8>(epi, p, s); return; }
+  launch_skinny_m<AM, 4, W8>(epi, p, s);
 }
 
 static void launch_skinny(int epi, const GemmArgs& g, hipStream_t s) {
@@ -599,6 +626,13 @@ static void launch_skinny(int epi, const GemmArgs& g, hipStream_t s) {
   p.a_group_cols = g.a_group_cols;
   p.msplit_n = g.msplit_n;
   p.ln_g = g.ln_g; p.ln_b = g.ln_b; p.ln_eps = g.ln_eps; p.ln_out = g.ln_out; p.ln_cnt = g.ln_cnt;
+  if (g.Wq) {  // int8 weights (W8A16): no LayerNorm form rides on it
+    JANUS_CHECK(g.wscale && !g.lnin_x && !g.ln_out && !g.ln_part,
+                "gemm: int8 weights need their row scales and take no LayerNorm prologue / epilogue");
+    p.Wq = g.Wq; p.wscale = g.wscale;
+    launch_skinny_t<AM_F16, true>(epi, p, s);
+    return;
+  }
   if (g.lnin_x) {  // A = LayerNorm(x) in the block's prologue (K <= 512)
     JANUS_CHECK(g.K <= 512 && g.K % 4 == 0, "skinny LayerNorm prologue: K <= 512, K % 4 == 0");
     p.x = g.lnin_x; p.ldx = g.lnin_ldx; p.lnin_g = g.lnin_g; p.lnin_b = g.lnin_b; p.eps = g.lnin_eps;
@@ -641,6 +675,8 @@ void gemm_launch(int epi, const GemmArgs& p, hipStream_t s) {
   JANUS_CHECK(p.M <= 64 || p.decode_rows || (epi != EPI_QKV && !p.lnin_x && p.a_group_cols == 0),
               "gemm: KV-cache / LayerNorm-prologue / grouped products above 64 rows are decoder steps "
               "(GemmArgs::decode_rows)");
+  JANUS_CHECK(!p.Wq || ((p.M <= 64 || (p.decode_rows && p.M <= kSkinnyMaxRows)) && ((uintptr_t)p.Wq & 7) == 0),
+              "gemm: int8 weights are the skinny kernel's (M <= 64, or a decoder step up to kSkinnyMaxRows), 8-byte aligned");
   if (p.M <= 64 || (p.decode_rows && p.M <= kSkinnyMaxRows)) launch_skinny(epi, p, s);
   else if (gemm_big_supported(epi, p)) gemm_big_launch(epi, p, s);
   else launch_cfg<128, 128, 4, 4>(epi, p, s);

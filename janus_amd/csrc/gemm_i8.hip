@@ -129,6 +129,47 @@ void quant_rows_f32_i8_launch(const float* x, int64_t ldx, int8_t* q, int64_t ld
   quant_rows_dispatch(x, ldx, q, ldq, scale, M, K, s);
 }
 
+// The prepare-time weight quantiser (the decoder's int8 weights; K reaches 5120): one wave per
+// fp16 row, the row read twice (amax, then q) instead of held in registers, so any K % 8 == 0.
+// The arithmetic is quant_rows_kernel's, operation for operation.
+__global__ __launch_bounds__(256) void quant_weight_rows_kernel(const _Float16* __restrict__ x, int64_t ldx,
+                                                                signed char* __restrict__ q, int64_t ldq,
+                                                                float* __restrict__ scale, int M, int K) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int nv = K / 8;
+  const _Float16* xr = x + (int64_t)row * ldx;
+  float v[8];
+  float amax = 0.0f;
+  for (int i = lane; i < nv; i += 64) {
+    load8(xr + 8 * i, v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+  }
+  amax = wave_max_f32(amax);
+  const float inv = amax == 0.0f ? 0.0f : quant_inv(amax);
+  if (lane == 0) scale[row] = quant_scale(amax);
+  for (int i = lane; i < nv; i += 64) {
+    load8(xr + 8 * i, v);
+    i8x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = quant_one(v[j], inv);
+    *reinterpret_cast<i8x8*>(q + (int64_t)row * ldq + 8 * i) = o;
+  }
+}
+
+void quant_weight_rows_i8_launch(const _Float16* x, int64_t ldx, int8_t* q, int64_t ldq, float* scale, int M,
+                                 int K, hipStream_t s) {
+  JANUS_CHECK(x && q && scale, "quant_weight_rows_i8: null argument");
+  JANUS_CHECK(K > 0 && K % 8 == 0, "quant_weight_rows_i8: K must be a multiple of 8");
+  JANUS_CHECK(ldx >= K && ldq >= K && ldx % 8 == 0 && ldq % 8 == 0, "quant_weight_rows_i8: row strides");
+  JANUS_CHECK(((uintptr_t)x & 15) == 0 && ((uintptr_t)q & 7) == 0, "quant_weight_rows_i8: alignment");
+  if (M <= 0) return;
+  quant_weight_rows_kernel<<<(M + 3) / 4, 256, 0, s>>>(x, ldx, reinterpret_cast<signed char*>(q), ldq, scale, M, K);
+  JANUS_LAUNCH_CHECK();
+}
+
 // layernorm_kernel (norm.hip) statement for statement up to the fp16 row, which stays in
 // registers and goes through the quantiser: bit-identical, q and scale, to layernorm_launch
 // followed by quant_rows_i8_launch.

@@ -148,6 +148,31 @@ extern "C" int janus_gemm_i8(int epi, const int8_t* A, int64_t lda, const int8_t
   });
 }
 
+extern "C" int janus_quant_weight_rows_i8(const uint16_t* x, int64_t ldx, int8_t* q, int64_t ldq, float* scale,
+                                          int M, int K, void* stream) {
+  return guarded([&] {
+    quant_weight_rows_i8_launch(reinterpret_cast<const _Float16*>(x), ldx, q, ldq, scale, M, K,
+                                (hipStream_t)stream);
+  });
+}
+
+extern "C" int janus_gemm_w8_f16(int epi, const uint16_t* A, int64_t lda, const int8_t* q, const float* scale,
+                                 int64_t ldw, const float* bias, void* C, int64_t ldc, const float* R,
+                                 int64_t ldr, int M, int N, int K, int a_group_cols, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(A && q && scale && C, "gemm_w8: null argument");
+    JANUS_CHECK(epi >= EPI_F16 && epi <= EPI_F32, "gemm_w8: epilogues 0 .. 3");
+    JANUS_CHECK(epi != EPI_RESID_F32 || R, "gemm_w8: the residual epilogue needs R");
+    GemmArgs g;
+    g.A = reinterpret_cast<const _Float16*>(A); g.lda = lda;
+    g.W = nullptr; g.Wq = q; g.wscale = scale; g.ldw = ldw;
+    g.bias = bias; g.C = C; g.ldc = ldc; g.R = R; g.ldr = ldr; g.M = M; g.N = N; g.K = K;
+    g.a_group_cols = a_group_cols;
+    g.decode_rows = true;   // up to kSkinnyMaxRows rows on the skinny kernel, as a decode step
+    gemm_launch(epi, g, (hipStream_t)stream);
+  });
+}
+
 extern "C" int janus_wave_xor_f32(const float* in, float* out, int n_waves, void* stream) {
   return guarded([&] {
     JANUS_CHECK(in && out, "null argument");
@@ -340,6 +365,50 @@ extern "C" int janus_logits_partial_hist_f16(const uint16_t* A, const uint16_t* 
   });
 }
 
+static int logits_partial_w8(const uint16_t* A, const int8_t* q, const float* scale, int K, int V, int batch,
+                             const DecodeRules& R, const uint8_t* smask, const int32_t* row_rules, int max_blocks,
+                             const uint32_t* seeds, int pos, void* parts, const uint32_t* hist,
+                             float repetition_penalty, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(A && q && scale && smask && row_rules && parts, "null argument");
+    JANUS_CHECK(batch >= 1 && batch <= kSkinnyMaxRows, "logits_partial: 1 <= batch <= 512");
+    logits_partial_launch(reinterpret_cast<const _Float16*>(A), K, nullptr, K, V, batch, R, smask,
+                          reinterpret_cast<const RowRules*>(row_rules), static_cast<LogitPart*>(parts),
+                          (hipStream_t)stream, nullptr, 0, nullptr, nullptr, max_blocks, seeds, pos, nullptr, nullptr,
+                          hist, repetition_penalty, q, scale);
+  });
+}
+
+extern "C" int janus_logits_partial_w8_f16(const uint16_t* A, const int8_t* q, const float* scale, int K, int V,
+                                           int batch, int eot, int suppress_blank, int blank, int ts_begin,
+                                           int no_timestamps, int max_initial_ts, int target,
+                                           const uint8_t* smask, const int32_t* row_rules, int max_blocks,
+                                           float inv_temp, const uint32_t* seeds, int pos, void* parts,
+                                           void* stream) {
+  DecodeRules R = beam_rules(eot, suppress_blank, blank, ts_begin, no_timestamps, max_initial_ts);
+  R.target = target;
+  R.inv_temp = inv_temp > 0.f ? inv_temp : 0.f;
+  return logits_partial_w8(A, q, scale, K, V, batch, R, smask, row_rules, max_blocks, seeds, pos, parts, nullptr,
+                           1.f, stream);
+}
+
+extern "C" int janus_logits_partial_hist_w8_f16(const uint16_t* A, const int8_t* q, const float* scale, int K,
+                                                int V, int batch, int eot, int suppress_blank, int blank,
+                                                int ts_begin, int no_timestamps, int max_initial_ts, int target,
+                                                const uint8_t* smask, const int32_t* row_rules, int max_blocks,
+                                                float inv_temp, const uint32_t* seeds, int pos, void* parts,
+                                                const uint32_t* hist, float repetition_penalty, void* stream) {
+  if (!hist || !(repetition_penalty > 0.f)) {
+    set_error("logits_partial_hist_w8: hist must be non-null and repetition_penalty > 0");
+    return -1;
+  }
+  DecodeRules R = beam_rules(eot, suppress_blank, blank, ts_begin, no_timestamps, max_initial_ts);
+  R.target = target;
+  R.inv_temp = inv_temp > 0.f ? inv_temp : 0.f;
+  return logits_partial_w8(A, q, scale, K, V, batch, R, smask, row_rules, max_blocks, seeds, pos, parts, hist,
+                           repetition_penalty, stream);
+}
+
 extern "C" int janus_beam_step(const void* parts, const void* tops, int nblk, int eot, int suppress_blank,
                                int blank, int ts_begin, int no_timestamps, int max_initial_ts,
                                int32_t* row_rules, int32_t* tokens, int ld, int pos, int32_t* done,
@@ -377,9 +446,10 @@ extern "C" int janus_decode_plan_describe(const janus_whisper_config* cfg, const
                                           int multi_lane, float temperature, const float* temperatures,
                                           int beam_size, const int32_t* stand, int n_stand, int stand_maxlen,
                                           char* text, int text_cap, int64_t* key, int key_cap, int32_t* n_key) {
-  return janus_decode_plan_describe_cross(cfg, opt, rows, batch, cus, resident, multi_lane, temperature,
+  return janus_decode_plan_describe_modes(cfg, opt, rows, batch, cus, resident, multi_lane, temperature,
                                           temperatures, beam_size, stand, n_stand, stand_maxlen,
-                                          JANUS_CROSS_COMPUTE_F16, text, text_cap, key, key_cap, n_key);
+                                          JANUS_CROSS_COMPUTE_F16, JANUS_DEC_COMPUTE_F16, text, text_cap, key,
+                                          key_cap, n_key);
 }
 
 extern "C" int janus_decode_plan_describe_cross(const janus_whisper_config* cfg, const janus_decode_options* opt,
@@ -388,6 +458,17 @@ extern "C" int janus_decode_plan_describe_cross(const janus_whisper_config* cfg,
                                                 int beam_size, const int32_t* stand, int n_stand,
                                                 int stand_maxlen, int cross_compute, char* text, int text_cap,
                                                 int64_t* key, int key_cap, int32_t* n_key) {
+  return janus_decode_plan_describe_modes(cfg, opt, rows, batch, cus, resident, multi_lane, temperature,
+                                          temperatures, beam_size, stand, n_stand, stand_maxlen, cross_compute,
+                                          JANUS_DEC_COMPUTE_F16, text, text_cap, key, key_cap, n_key);
+}
+
+extern "C" int janus_decode_plan_describe_modes(const janus_whisper_config* cfg, const janus_decode_options* opt,
+                                                const janus_decode_rows* rows, int batch, int cus, int resident,
+                                                int multi_lane, float temperature, const float* temperatures,
+                                                int beam_size, const int32_t* stand, int n_stand,
+                                                int stand_maxlen, int cross_compute, int dec_compute, char* text,
+                                                int text_cap, int64_t* key, int key_cap, int32_t* n_key) {
   return guarded([&] {
     JANUS_CHECK(cfg && opt && text && key && n_key, "null argument");
     JANUS_CHECK(batch >= 1, "decode: batch must be >= 1");
@@ -400,7 +481,7 @@ extern "C" int janus_decode_plan_describe_cross(const janus_whisper_config* cfg,
     seg.resident = [resident](int, int) { return resident != 0; };
     const DecodePlan P = plan_decode(*cfg, *opt, rows, (temperatures || temperature > 0.f) ? &smp : nullptr,
                                      beam_size > 0 ? &bm : nullptr, batch, cus, multi_lane != 0,
-                                     LaneStand{&st, stand_maxlen}, seg, cross_compute);
+                                     LaneStand{&st, stand_maxlen}, seg, cross_compute, dec_compute);
     const std::string d = P.describe();
     std::vector<int64_t> k;
     P.append_key(k);

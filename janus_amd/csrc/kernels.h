@@ -44,6 +44,11 @@ struct GemmArgs {
   // LayerNorm launch (A / lda are then unused).
   const float* lnin_x = nullptr; int64_t lnin_ldx = 0;
   const float* lnin_g = nullptr; const float* lnin_b = nullptr; float lnin_eps = 1e-5f;
+  // int8 weights (W8A16, skinny kernel only: M <= 64, or decode_rows up to kSkinnyMaxRows):
+  // Wq int8 [N][K] (row stride ldw, 8-byte aligned) and wscale [N] replace W:
+  // y[m][n] = wscale[n] * sum_k A[m][k] * fp16(Wq[n][k]) + bias[n] (fp16 MFMA, fp32 accumulation,
+  // scale and bias in fp32), then the epilogue. No LayerNorm prologue / epilogue form.
+  const int8_t* Wq = nullptr; const float* wscale = nullptr;
 };
 void gemm_launch(int epi, const GemmArgs& p, hipStream_t s);
 // the general large-M kernel (128 x 128 tiles, any N / K % 8), for shapes gemm_big rejects
@@ -96,6 +101,10 @@ void quant_rows_f32_i8_launch(const float* x, int64_t ldx, int8_t* q, int64_t ld
                               int K, hipStream_t s);
 // layernorm_launch followed by quant_rows_i8_launch in one pass, bit for bit; the fp16 row
 // is never written. d % 16 == 0, d <= 2048.
+// The prepare-time weight quantiser: quant_rows_i8_launch's arithmetic on fp16 rows of any
+// K % 8 == 0 (two passes over the row, nothing held in registers): the decoder's int8 weights.
+void quant_weight_rows_i8_launch(const _Float16* x, int64_t ldx, int8_t* q, int64_t ldq, float* scale, int M,
+                                 int K, hipStream_t s);
 void layernorm_quant_i8_launch(const float* x, const float* g, const float* b, int8_t* q, float* scale,
                                int rows, int d, float eps, hipStream_t s);
 // C[M,N] = epi( float(sum_k A[m,k] W[n,k]) * (a_scale[m] * w_scale[n]) + bias[n] ), int32

@@ -137,6 +137,21 @@ __device__ __forceinline__ void st_act(_Float16* p, const half8& v) {
   __builtin_nontemporal_store(v, reinterpret_cast<half8*>(p));
 }
 
+// 8 int8 weights -> 8 fp16, exact (every int8 value is an fp16): the bytes with their sign
+// bit flipped (q + 128 in 0 .. 255) are permuted under the exponent byte 0x64, which reads as
+// the fp16 1024 + (q + 128) (ulp 1 in [1024, 2048)), and one packed subtract of 1152 leaves q.
+// 4 v_perm_b32 + 2 v_xor + 4 v_pk_add_f16 per 8 weights. Element j is byte j.
+__device__ __forceinline__ half8 w8_half8(uint2 q) {
+  const unsigned lo = q.x ^ 0x80808080u, hi = q.y ^ 0x80808080u;
+  constexpr unsigned ex = 0x64646464u;  // selector bytes 0-3: the weights' bytes, 4-7: ex's
+  const u32x4 u = {__builtin_amdgcn_perm(ex, lo, 0x04010400u), __builtin_amdgcn_perm(ex, lo, 0x04030402u),
+                   __builtin_amdgcn_perm(ex, hi, 0x04010400u), __builtin_amdgcn_perm(ex, hi, 0x04030402u)};
+  half8 off;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) off[j] = (_Float16)1152.0f;
+  return __builtin_bit_cast(half8, u) - off;
+}
+
 __device__ __forceinline__ half8 zero_half8() {
   half8 z;
 #pragma unroll

@@ -87,6 +87,7 @@ void prepare(janus_whisper* w, hipStream_t s) {
   }
   w->dec.clear();
   w->dec.resize(c.dec_layers);
+  w->dec_i8_prepared = false;  // likewise the decoder's
   for (int l = 0; l < c.dec_layers; ++l) {
     const std::string p = "decoder.layers." + std::to_string(l) + ".";
     DecLayer& L = w->dec[l];
@@ -155,6 +156,32 @@ static void prepare_i8(janus_whisper* w, hipStream_t s) {
   }
   JANUS_HIP(hipStreamSynchronize(s));
   w->i8_prepared = true;
+}
+
+// The int8 copies of the decoder's weights (janus_whisper_set_decoder_compute): every matrix the
+// decode call multiplies, quantised per output row from its prepared fp16 copy — the absorbed
+// query weight from its absorbed form — and the token embedding as the vocabulary table.
+void prepare_dec_i8(janus_whisper* w, hipStream_t s) {
+  if (w->dec_i8_prepared) return;
+  const auto& c = w->cfg;
+  JANUS_CHECK(xattn_supported(c.d_model, c.n_heads), "int8 decoder weights: no absorbed cross-attention at this shape");
+  int64_t N, K;
+  for (int l = 0; l < c.dec_layers; ++l) {
+    DecLayer& L = w->dec[l];
+    for (int i = 0; i < 7; ++i) {
+      dec_weight_shape(c, i, &N, &K);
+      L.q8[i].ensure((size_t)N * K);
+      L.s8[i].ensure(sizeof(float) * N);
+      quant_weight_rows_i8_launch(L.w16(i).as<_Float16>(), K, L.q8[i].as<int8_t>(), K, L.s8[i].as<float>(), (int)N,
+                                  (int)K, s);
+    }
+  }
+  dec_weight_shape(c, -1, &N, &K);
+  w->tokq.ensure((size_t)N * K);
+  w->toks.ensure(sizeof(float) * N);
+  quant_weight_rows_i8_launch(w->tok16.as<_Float16>(), K, w->tokq.as<int8_t>(), K, w->toks.as<float>(), (int)N, (int)K, s);
+  JANUS_HIP(hipStreamSynchronize(s));
+  w->dec_i8_prepared = true;
 }
 
 // The encoder's projections (M = B * 1500 rows): gemm_launch dispatches them to the
@@ -365,5 +392,45 @@ extern "C" int janus_whisper_cross_compute(janus_whisper* w, int32_t* mode) {
     JANUS_CHECK(w && mode, "null argument");
     std::lock_guard<std::mutex> lk(w->mu);
     *mode = w->cross_compute;
+  });
+}
+
+extern "C" int janus_whisper_set_decoder_compute(janus_whisper* w, int mode) {
+  return guarded([&] {
+    JANUS_CHECK(w, "null argument");
+    JANUS_CHECK(mode == JANUS_DEC_COMPUTE_F16 || mode == JANUS_DEC_COMPUTE_INT8,
+                "decoder compute: 0 (float16) or 1 (int8)");
+    if (mode == JANUS_DEC_COMPUTE_INT8)
+      JANUS_CHECK(xattn_supported(w->cfg.d_model, w->cfg.n_heads),
+                  "int8 decoder weights: d_model must be 384, 512, 768, 1024 or 1280 with 64-wide heads");
+    std::lock_guard<std::mutex> lk(w->mu);
+    // (as the cross mode: the plan's key word keeps the two modes' captured graphs apart, so a
+    // call after a switch never replays the other mode's launches)
+    w->dec_compute = mode;
+  });
+}
+
+extern "C" int janus_whisper_decoder_compute(janus_whisper* w, int32_t* mode) {
+  return guarded([&] {
+    JANUS_CHECK(w && mode, "null argument");
+    std::lock_guard<std::mutex> lk(w->mu);
+    *mode = w->dec_compute;
+  });
+}
+
+extern "C" int janus_whisper_decoder_weight_i8(janus_whisper* w, int layer, int which, int8_t* q_out, float* s_out) {
+  return guarded([&] {
+    JANUS_CHECK(w && q_out && s_out, "null argument");
+    JANUS_CHECK(layer >= -1 && layer < w->cfg.dec_layers, "decoder_weight_i8: layer must be -1 .. dec_layers - 1");
+    JANUS_CHECK(layer < 0 || (which >= 0 && which < 7), "decoder_weight_i8: which must be a JANUS_DEC_W_*");
+    std::lock_guard<std::mutex> lk(w->mu);
+    prepare(w, nullptr);
+    prepare_dec_i8(w, nullptr);
+    int64_t N, K;
+    dec_weight_shape(w->cfg, layer < 0 ? -1 : which, &N, &K);
+    const DevMem& q = layer < 0 ? w->tokq : w->dec[layer].q8[which];
+    const DevMem& sc = layer < 0 ? w->toks : w->dec[layer].s8[which];
+    JANUS_HIP(hipMemcpy(q_out, q.p, (size_t)N * K, hipMemcpyDeviceToHost));
+    JANUS_HIP(hipMemcpy(s_out, sc.p, sizeof(float) * N, hipMemcpyDeviceToHost));
   });
 }

@@ -22,6 +22,14 @@ struct EncLayer {
 struct DecLayer {
   DevMem wqkv, bqkv, wo, wq_c, wk_c, wv_c, wo_c, w1, w2;
   DevMem wqk, bqk;  // absorbed cross-attention query weights (xattn.hip)
+  // int8 copies of the seven matrices the decode call multiplies and their row scales,
+  // quantised from the fp16 copies above (prepare_dec_i8: made when the int8 decoder weights
+  // are first used), indexed by JANUS_DEC_W_*
+  DevMem q8[7], s8[7];
+  const DevMem& w16(int which) const {
+    const DevMem* m[7] = {&wqkv, &wo, &wqk, &wv_c, &wo_c, &w1, &w2};
+    return *m[which];
+  }
   const float *bo, *bq_c, *bv_c, *bo_c, *b1, *b2;
   const float *ln1g, *ln1b, *ln2g, *ln2b, *ln3g, *ln3b;
 };
@@ -45,6 +53,7 @@ struct DecLane {
   // their encoder output (JANUS_ENC_ROWS_*) and the persistent level it ran (0: launches)
   int last_enc_rows = 0, last_persist = 0;
   int last_cross = 0;            // JANUS_CROSS_COMPUTE_* the last call ran (janus_whisper_decode_cross)
+  int last_weights = 0;          // JANUS_DEC_COMPUTE_* the last call ran (janus_whisper_decode_weights)
   int last_positions = 0;        // positions the last decode stepped
   int64_t last_launches = 0;     // kernel launches those positions issued (graph nodes)
   // where each row slot stands after the last call (positions whose KV rows and next
@@ -88,9 +97,12 @@ struct janus_whisper {
   int enc_compute = JANUS_ENC_COMPUTE_F16;  // janus_whisper_set_encoder_compute
   bool i8_prepared = false;                 // the encoder layers hold their int8 weights
   int cross_compute = JANUS_CROSS_COMPUTE_F16;  // janus_whisper_set_cross_compute
+  int dec_compute = JANUS_DEC_COMPUTE_F16;      // janus_whisper_set_decoder_compute
+  bool dec_i8_prepared = false;                 // the decoder layers and tokq hold their int8 weights
   std::mutex mu;
   // device-side prepared weights
   janus::DevMem conv1p, conv2p, pos16, tok16;
+  janus::DevMem tokq, toks;  // int8 decoder weights: the vocabulary projection's table and row scales
   std::vector<janus::EncLayer> enc;
   std::vector<janus::DecLayer> dec;
   // workspaces
@@ -113,6 +125,15 @@ namespace janus {
 
 // the device-side weights from the uploaded parameters (whisper.cpp; no-op once prepared)
 void prepare(janus_whisper* w, hipStream_t s);
+// the int8 copies of the decoder's weights (whisper.cpp; after prepare, no-op once made)
+void prepare_dec_i8(janus_whisper* w, hipStream_t s);
+// rows and columns of a decoder layer's matrix JANUS_DEC_W_* (which), or of the vocabulary table (-1)
+inline void dec_weight_shape(const janus_whisper_config& c, int which, int64_t* N, int64_t* K) {
+  const int64_t d = c.d_model;
+  *K = which == JANUS_DEC_W_FC2 ? 4 * d : d;
+  *N = which < 0 ? c.n_vocab : which == JANUS_DEC_W_QKV ? 3 * d : which == JANUS_DEC_W_XQK ? c.n_heads * d
+       : which == JANUS_DEC_W_FC1 ? 4 * d : d;
+}
 
 inline GemmArgs gargs(const _Float16* A, int64_t lda, const _Float16* W, int64_t ldw,
                       const float* bias, void* C, int64_t ldc, int M, int N, int K,

@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from ..tokenizer import TASKS
-from ..whisper import check_beam_args, check_family_features, check_history_args, resolve_suppress_tokens
+from ..whisper import (check_beam_args, check_decoder_compute_beam, check_family_features, check_history_args,
+                       resolve_suppress_tokens)
 from . import transcriber as tr
 from . import vad_filter as vf
 
@@ -152,6 +153,7 @@ def generate_segments_batched(engine, audios, batch_size: int = 64, max_length: 
     ``stats`` (a dict, measurement only): filled with ``rounds`` (rows of every round) and the
     host seconds spent in ``vad_rule``, ``chunking`` and ``text``."""
     check_beam_args(beam_size, length_penalty)
+    check_decoder_compute_beam(getattr(engine, "decoder_compute", "float16"), beam_size)
     check_family_features(getattr(engine, "cfg", None), beam_size, word_timestamps,
                           getattr(engine, "alignment_heads", None))
     check_history_args(repetition_penalty, no_repeat_ngram_size, beam_size)
@@ -367,6 +369,7 @@ class BatchedInferencePipeline:
         mode decodes once at T = 0 and applies no gate."""
         m = self.model
         check_beam_args(beam_size, length_penalty, patience)
+        check_decoder_compute_beam(getattr(m, "decoder_compute", "float16"), beam_size)
         check_history_args(repetition_penalty, no_repeat_ngram_size, beam_size)
         check_family_features(getattr(m.engine, "cfg", None), beam_size, word_timestamps,
                               getattr(m.engine, "alignment_heads", None))

@@ -61,8 +61,9 @@ from .. import _native as nat
 from ..audio import decode_audio
 from ..common import wavio
 from ..tokenizer import LANGUAGES, SOT_PREV, TASKS
-from ..whisper import (CONFIGS, WhisperEngine, check_beam_args, check_encoder_compute,
-                       check_family_features, check_history_args, cross_compute_mode, resolve_model,
+from ..whisper import (CONFIGS, WhisperEngine, check_beam_args, check_decoder_compute_beam, check_encoder_compute,
+                       check_family_features, check_history_args, cross_compute_mode, decoder_compute_mode,
+                       resolve_model,
                        resolve_suppress_tokens, shared_rows_in_place)
 from . import vad_filter as vf
 
@@ -753,6 +754,7 @@ def generate_segments(engine: WhisperEngine, audios, max_batch: int = 64, max_le
     and no result differs.
     Returns one _Stream (segments + gate counters) per utterance."""
     check_beam_args(beam_size, length_penalty)
+    check_decoder_compute_beam(getattr(engine, "decoder_compute", "float16"), beam_size)
     check_family_features(getattr(engine, "cfg", None), beam_size, word_timestamps,
                           getattr(engine, "alignment_heads", None))
     check_history_args(repetition_penalty, no_repeat_ngram_size, beam_size)
@@ -908,7 +910,8 @@ class WhisperModel:
     ``int8_bfloat16`` run the encoder's linear layers (QKV, out_proj, fc1, fc2) in int8 on
     the i8 MFMA with CTranslate2's row-wise symmetric quantisation, and every other accepted
     value runs them in fp16. The conv stem, attention, LayerNorms and the whole decoder are
-    fp16 weights on MFMA with fp32 accumulation in every case. With the
+    fp16 weights on MFMA with fp32 accumulation whatever ``compute_type`` says (DESIGN.md §5j;
+    the decoder's weights have their own keyword, ``decoder_compute``, below). With the
     default ``apply_compute_type=False`` every ``compute_type`` runs fp16 — what
     ``Transcriber`` gets, whose parity tests against the fp32 oracle depend on it.
     ``effective_compute_type`` reports what runs: ``"float16"`` or ``"int8_float16"``.
@@ -918,6 +921,11 @@ class WhisperModel:
     cross-attention streams those (WhisperEngine); the word alignment and the
     language detection keep the fp16 rows. ValueError for any other name but ``"float16"``.
 
+    ``decoder_compute="int8"`` (opt-in, its own keyword: ``compute_type`` keeps meaning what it
+    means above) is passed to the engine: every decoder linear layer and the vocabulary
+    projection multiply int8 weights (WhisperEngine). ``beam_size`` > 1 is then a
+    NotImplementedError before any GPU work. ValueError for any other name but ``"float16"``.
+
     ``audio_resample`` says how a file (a path, a PathLike, an open binary file or bytes)
     becomes 16 kHz audio: ``"reference"`` (the default) is ``read_wav_16k``, the reference's
     ``[::3]`` at 48 kHz and linear interpolation elsewhere; ``"bandlimited"`` is
@@ -926,8 +934,11 @@ class WhisperModel:
 
     def __init__(self, model_size: str, device: str = "auto", compute_type: str = "default",
                  *, apply_compute_type: bool = False, vad_weights: dict = None, alignment_heads=None,
-                 cross_compute: str = "float16", audio_resample: str = "reference", **_ignored):
+                 cross_compute: str = "float16", audio_resample: str = "reference",
+                 decoder_compute: str = "float16", **_ignored):
         cross_compute_mode(cross_compute)   # ValueError: unknown name
+        decoder_compute_mode(decoder_compute)   # ValueError: unknown name
+        self.decoder_compute = decoder_compute
         self._audio_resample = audio_resample_mode(audio_resample)   # ValueError: unknown name
         model_size = resolve_model(model_size)   # ValueError: unknown; "turbo" -> "large-v3-turbo"
         if device not in DEVICES:
@@ -941,6 +952,8 @@ class WhisperModel:
         kw = {} if alignment_heads is None else {"alignment_heads": alignment_heads}
         if cross_compute != "float16":
             kw["cross_compute"] = cross_compute
+        if decoder_compute != "float16":
+            kw["decoder_compute"] = decoder_compute
         self.engine = WhisperEngine(CONFIGS[model_size], encoder_compute=enc_compute, **kw)
         self.stats = {"windows": 0, "needs_fallback": 0, "no_speech_skips": 0, "fallback_decodes": 0}
         # vad_filter: silero weights (default: JANUS_VAD_DIR; none: the energy stand-in); the
@@ -1048,6 +1061,7 @@ class WhisperModel:
         faster-whisper (generate_segments): the two history rules need
         ``beam_size`` 1 (NotImplementedError otherwise, before any GPU work)."""
         check_beam_args(beam_size, length_penalty, patience)
+        check_decoder_compute_beam(getattr(self, "decoder_compute", "float16"), beam_size)
         check_history_args(repetition_penalty, no_repeat_ngram_size, beam_size)
         check_family_features(getattr(self.engine, "cfg", None), beam_size, word_timestamps,
                               getattr(self.engine, "alignment_heads", None))

@@ -419,6 +419,26 @@ def cross_compute_mode(name) -> int:
     return CROSS_COMPUTE[name]
 
 
+# compute types of the decoder's weights (janus.h JANUS_DEC_COMPUTE_*)
+DECODER_COMPUTE = {"float16": 0, "int8": 1}
+DECODER_COMPUTE_NAMES = ("float16", "int8")
+
+
+def decoder_compute_mode(name) -> int:
+    """"float16" / "int8" -> JANUS_DEC_COMPUTE_*; ValueError for anything else."""
+    if not isinstance(name, str) or name not in DECODER_COMPUTE:
+        raise ValueError(f"decoder_compute must be one of {sorted(DECODER_COMPUTE)}, not {name!r}")
+    return DECODER_COMPUTE[name]
+
+
+def check_decoder_compute_beam(decoder_compute: str, beam_size: int) -> None:
+    """Beam search has no int8-weight form (the vocabulary projection's beam partials read the
+    fp16 table): NotImplementedError for beam_size > 1 with decoder_compute "int8"."""
+    if decoder_compute_mode(decoder_compute) != DECODER_COMPUTE["float16"] and beam_size > 1:
+        raise NotImplementedError(f"beam_size {beam_size} with decoder_compute='int8': beam search multiplies the "
+                                  "float16 decoder weights only; use beam_size=1 or decoder_compute='float16'")
+
+
 ALIGN_MAX_HEADS = 64   # alignment heads of one engine (csrc/align_plan.h kAlignMaxHeads)
 
 
@@ -463,20 +483,26 @@ class WhisperEngine:
 
     encoder_compute: "float16" (default: fp16 weights and activations on the fp16 MFMA) or
     "int8" (the encoder's QKV / out_proj / fc1 / fc2 on the i8 MFMA with row-wise symmetric
-    quantisation, CTranslate2's int8 compute type). The decoder's weights are
-    fp16 in both.
+    quantisation, CTranslate2's int8 compute type). It leaves the decoder alone.
 
     cross_compute: "float16" (default: the decoder's cross-attention streams the encoder
     output it is handed) or "int8" (every decode call quantises its encoder rows per key to
     int8 first, CTranslate2's rule for the input of the cross-attention K / V projections, and
     the cross-attention streams those: half the bytes; include/janus.h
     janus_whisper_set_cross_compute). align() and detect_language() read the
-    fp16 rows in both."""
+    fp16 rows in both.
+
+    decoder_compute: "float16" (default) or "int8": every decoder linear layer and the
+    vocabulary projection multiply int8 weights (per-row scales, fp16 activations, W8A16;
+    include/janus.h janus_whisper_set_decoder_compute) on the unfused launch
+    path. Greedy and sampled calls; decode_beam() is refused. The fp16 weights stay resident."""
 
     def __init__(self, cfg: WhisperConfig, weights: dict = None, seed: int = 0,
-                 encoder_compute: str = "float16", alignment_heads=None, cross_compute: str = "float16"):
+                 encoder_compute: str = "float16", alignment_heads=None, cross_compute: str = "float16",
+                 decoder_compute: str = "float16"):
         mode = encoder_compute_mode(encoder_compute)
         cross = cross_compute_mode(cross_compute)
+        dmode = decoder_compute_mode(decoder_compute)
         check_encoder_compute(cfg, mode)
         if alignment_heads is not None:
             alignment_heads = check_alignment_heads(cfg, alignment_heads)
@@ -500,6 +526,8 @@ class WhisperEngine:
             nat.call("janus_whisper_set_encoder_compute", self._h, mode)
         if cross != CROSS_COMPUTE["float16"]:
             nat.call("janus_whisper_set_cross_compute", self._h, cross)
+        if dmode != DECODER_COMPUTE["float16"]:
+            nat.call("janus_whisper_set_decoder_compute", self._h, dmode)
         self.alignment_heads = alignment_heads or default_alignment_heads(cfg)
         if alignment_heads is not None:
             pairs = np.ascontiguousarray(np.asarray(alignment_heads, np.int32).reshape(-1, 2))
@@ -530,6 +558,40 @@ class WhisperEngine:
         direction, between calls); "float16" again is bit-identical to never having left it."""
         m = cross_compute_mode(mode)   # ValueError: unknown name
         nat.call("janus_whisper_set_cross_compute", self._h, m)
+
+    @property
+    def decoder_compute(self) -> str:
+        """The weights the next decode call multiplies: "float16" | "int8"."""
+        m = ctypes.c_int32(-1)
+        nat.call("janus_whisper_decoder_compute", self._h, ctypes.addressof(m))
+        return DECODER_COMPUTE_NAMES[m.value]
+
+    def set_decoder_compute(self, mode: str) -> None:
+        """Switch the decoder's weights between "float16" and "int8" (either direction, between
+        calls); the int8 copies are quantised on the first int8 decode call, "float16" again is
+        bit-identical to never having left it."""
+        m = decoder_compute_mode(mode)   # ValueError: unknown name
+        nat.call("janus_whisper_set_decoder_compute", self._h, m)
+
+    def decode_weights(self) -> str:
+        """The weights the last decode call multiplied (janus_whisper_decode_weights):
+        "float16" | "int8"."""
+        m = ctypes.c_int32(0)
+        nat.call("janus_whisper_decode_weights", self._h, ctypes.addressof(m))
+        return DECODER_COMPUTE_NAMES[int(m.value)]
+
+    def decoder_weight_i8(self, layer: int, which: int):
+        """(q int8 [N][K], s float32 [N]) of one quantised decoder matrix as the int8 mode
+        multiplies it (janus_whisper_decoder_weight_i8, test entry): ``which`` a
+        DEC_W_* index of layer ``layer``, or layer -1: the vocabulary table."""
+        d, c = self.cfg.d_model, self.cfg
+        n, k = ((c.n_vocab, d) if layer < 0 else
+                {0: (3 * d, d), 1: (d, d), 2: (c.n_heads * d, d), 3: (d, d), 4: (d, d), 5: (4 * d, d),
+                 6: (d, 4 * d)}[int(which)])
+        q = np.empty((n, k), np.int8)
+        s = np.empty(n, np.float32)
+        nat.call("janus_whisper_decoder_weight_i8", self._h, int(layer), int(which), q.ctypes.data, s.ctypes.data)
+        return q, s
 
     def set_tensor(self, name: str, arr) -> None:
         """Re-upload one parameter (janus_whisper_set_tensor); the next call re-prepares
@@ -739,6 +801,9 @@ class WhisperEngine:
         windows x beam_size <= 512; staggered rows (``pos_offset``) and ``temperature`` > 0
         are rejected, a ``persistent`` request runs the launch path (decode_path())."""
         check_beam_args(beam_size, length_penalty)
+        if getattr(self, "_h", None) is not None and self.decoder_compute != "float16":
+            raise NotImplementedError("decode_beam with decoder_compute='int8': beam search multiplies the float16 "
+                                      "decoder weights only")
         check_family_features(getattr(self, "cfg", None), beam_size)   # (beam_size 1 there: the C entry refuses)
         if pos_offset is not None:
             raise ValueError("decode_beam: staggered rows (pos_offset) are not supported")
@@ -977,6 +1042,9 @@ class WhisperEngine:
         pl = prompt_lens if prompt_lens is not None else [plen] * len(t)
         return [self.tokenizer.transcript(row[int(p):]) for row, p in zip(t, pl)]
 
+
+# janus_whisper_decoder_weight_i8 `which` (include/janus.h JANUS_DEC_W_*)
+DEC_W_QKV, DEC_W_O, DEC_W_XQK, DEC_W_XV, DEC_W_XO, DEC_W_FC1, DEC_W_FC2 = range(7)
 
 # janus_whisper_decode_path enc_rows (include/janus.h JANUS_ENC_ROWS_*)
 ENC_ROWS_NAMES = ("own", "in_place", "gathered")
