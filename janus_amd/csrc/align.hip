@@ -124,12 +124,7 @@ void align_attention_launch(const AlignAttnArgs& a, int n_tiles, int H, int max_
   JANUS_CHECK(max_keys >= 1 && max_keys <= 2048, "align attention: 1 .. 2048 keys");
   if (n_tiles <= 0) return;
   const size_t lds = (size_t)kAlignTileRows * (((max_keys + 31) & ~31) + 4) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)align_attn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<align_attn_kernel>(160 * 1024);
   align_attn_kernel<<<dim3(n_tiles, H), 256, lds, s>>>(a);
   JANUS_LAUNCH_CHECK();
 }

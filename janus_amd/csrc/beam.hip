@@ -236,23 +236,15 @@ __global__ __launch_bounds__(256) void beam_step_kernel(
   }
 }
 
-void beam_step_launch(const LogitPart* parts, const BeamTop* tops, int nblk, const DecodeRules& R,
-                      RowRules* rules, int32_t* tokens, int ld, int pos, int32_t* done,
-                      float* sum_lp, int32_t* n_tok, const int32_t* plen, float* nsp,
-                      const BeamState& st, int W, hipStream_t s) {
+void beam_step_launch(const SelectArgs& a, const BeamTop* tops, const BeamState& st, int W, hipStream_t s) {
   JANUS_CHECK(st.k >= 1 && st.k <= kBeamMax, "beam_step: beam size must be 1 .. 8");
-  JANUS_CHECK(nblk >= 1 && nblk <= 256, "beam_step: 1 .. 256 partials per row");
-  JANUS_CHECK(ld <= kBeamTokMax && pos + 1 < ld, "beam_step: max_length <= 448, pos + 1 < max_length");
-  JANUS_CHECK(plen, "beam_step: per-row prompt lengths needed");
-  const size_t lds = (size_t)4 * 2 * st.k * nblk * sizeof(unsigned long long);
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)beam_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  4 * kBeamTop * 256 * (int)sizeof(unsigned long long)));
-    attr = true;
-  }
-  beam_step_kernel<<<W, 256, lds, s>>>(parts, tops, nblk, R, rules, tokens, ld, pos, done, sum_lp, n_tok,
-                                       plen, nsp, st);
+  JANUS_CHECK(a.nblk >= 1 && a.nblk <= 256, "beam_step: 1 .. 256 partials per row");
+  JANUS_CHECK(a.ld <= kBeamTokMax && a.pos + 1 < a.ld, "beam_step: max_length <= 448, pos + 1 < max_length");
+  JANUS_CHECK(a.plen, "beam_step: per-row prompt lengths needed");
+  const size_t lds = (size_t)4 * 2 * st.k * a.nblk * sizeof(unsigned long long);
+  allow_dynamic_lds<beam_step_kernel>(4 * kBeamTop * 256 * (int)sizeof(unsigned long long));
+  beam_step_kernel<<<W, 256, lds, s>>>(a.parts, tops, a.nblk, a.R, a.rules, a.tokens, a.ld, a.pos, a.done,
+                                       a.sum_lp, a.n_tok, a.plen, a.nsp, st);
   JANUS_LAUNCH_CHECK();
 }
 

@@ -10,8 +10,10 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <mutex>
 #include <string>
 #include <stdexcept>
+#include <type_traits>
 #include "errors.h"
 
 namespace janus {
@@ -31,6 +33,31 @@ int stream_cu_count(hipStream_t s);
 
 // Launch check after <<<>>> (launch config errors surface here, not faults).
 #define JANUS_LAUNCH_CHECK() JANUS_HIP(hipGetLastError())
+
+// The opt-in a kernel needs before it launches with more than 64 KB of dynamic LDS
+// (hipFuncAttributeMaxDynamicSharedMemorySize), made once per kernel per process. The
+// once-flag belongs to the instantiation, so it cannot disagree with the kernel it guards, and
+// launchers that run on several host threads (one per decode lane) may arrive together.
+// One flag per process, not per device: the library runs one device per process.
+template <auto Kernel>
+void allow_dynamic_lds(int bytes) {
+  static std::once_flag once;
+  std::call_once(once, [bytes] {
+    JANUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  });
+}
+
+// A kernel chosen at run time travels with its opt-in: what a launcher's kernel table holds.
+template <class Fn>
+struct LdsKernel {
+  Fn* fn;
+  void (*allow)(int bytes);
+};
+template <auto Kernel>
+constexpr LdsKernel<std::remove_pointer_t<decltype(Kernel)>> lds_kernel() {
+  return {Kernel, &allow_dynamic_lds<Kernel>};
+}
 
 constexpr int kWave = 64;  // CDNA wavefront width (never 32)
 

@@ -331,13 +331,8 @@ static void conv_cfg(const ConvArgs& a, hipStream_t s) {
   const size_t lds = lds_loop > lds_epi ? lds_loop : lds_epi;
   JANUS_CHECK(lds <= 160 * 1024, "conv: LDS tile too large (" + std::to_string(lds) + " B)");
   const int blocks = (int)(cdiv(a.n_rows, BM) * cdiv(a.Cout, BN));
-  auto kern = conv_kernel<BM, BN, WMT, WNT, CK, PRE, POST>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024));
-    attr_set = true;
-  }
+  constexpr auto kern = conv_kernel<BM, BN, WMT, WNT, CK, PRE, POST>;
+  allow_dynamic_lds<kern>(160 * 1024);
   kern<<<dim3(blocks, a.phases, a.B), 256, lds, s>>>(a, rows_max);
   JANUS_LAUNCH_CHECK();
 }

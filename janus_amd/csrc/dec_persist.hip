@@ -1213,10 +1213,6 @@ bool dec_seg_supported(int d, int H, int B, int cus) {
   return d == kD && H == 8 && dec_seg_grid(B, cus) > 0;
 }
 
-static void seg_attr(const void* k, size_t lds = kSegLds) {
-  JANUS_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-}
-
 bool dec_seg_resident(int grid, int cus) { return (int64_t)seg_per_cu() * cus >= grid; }
 
 // co-resident blocks per CU of the segment kernels: the most demanding launch, the layer
@@ -1226,8 +1222,8 @@ static int seg_per_cu() {
   if (per_cu < 0) {
     const size_t lds = std::max(kSegLds, (size_t)kXattnLds);
     int a = 0, b = 0;
-    seg_attr((const void*)dec_layer_kernel<false>, lds);
-    seg_attr((const void*)dec_layer_kernel<true>, lds);
+    allow_dynamic_lds<dec_layer_kernel<false>>((int)lds);
+    allow_dynamic_lds<dec_layer_kernel<true>>((int)lds);
     JANUS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, dec_layer_kernel<false>, kNT, lds));
     JANUS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, dec_layer_kernel<true>, kNT, lds));
     per_cu = std::min(a, b);
@@ -1244,8 +1240,7 @@ static bool seg_big(const DecSegArgs& a, int grid) { return grid < 16 * a.MT; }
 
 template <bool BIG>
 static void seg_a_go(const DecSegArgs& a, int grid, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) { seg_attr((const void*)dec_seg_a_kernel<BIG>); attr = true; }
+  allow_dynamic_lds<dec_seg_a_kernel<BIG>>((int)kSegLds);
   dec_seg_a_kernel<BIG><<<grid, kNT, kSegLds, s>>>(a);
   JANUS_LAUNCH_CHECK();
 }
@@ -1256,8 +1251,7 @@ void dec_seg_a_launch(const DecSegArgs& a, int grid, hipStream_t s) {
 
 template <bool BIG>
 static void seg_b_go(const DecSegArgs& a, int grid, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) { seg_attr((const void*)dec_seg_b_kernel<BIG>); attr = true; }
+  allow_dynamic_lds<dec_seg_b_kernel<BIG>>((int)kSegLds);
   dec_seg_b_kernel<BIG><<<grid, kNT, kSegLds, s>>>(a);
   JANUS_LAUNCH_CHECK();
 }
@@ -1268,8 +1262,7 @@ void dec_seg_b_launch(const DecSegArgs& a, int grid, hipStream_t s) {
 
 template <bool BIG>
 static void layer_go(const DecSegArgs& b, const DecSegNext& nx, int grid, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) { seg_attr((const void*)dec_layer_kernel<BIG>, std::max(kSegLds, (size_t)kXattnLds)); attr = true; }
+  allow_dynamic_lds<dec_layer_kernel<BIG>>((int)std::max(kSegLds, (size_t)kXattnLds));
   dec_layer_kernel<BIG><<<grid, kNT, layer_lds(b), s>>>(b, nx);
   JANUS_LAUNCH_CHECK();
 }
@@ -1285,8 +1278,7 @@ void dec_layer_launch(const DecSegArgs& b, const DecSegNext& nx, int grid, hipSt
 
 template <bool BIG>
 static void head_go(const DecSegArgs& g, int grid, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) { seg_attr((const void*)dec_head_kernel<BIG>, std::max(kSegLds, (size_t)kXattnLds)); attr = true; }
+  allow_dynamic_lds<dec_head_kernel<BIG>>((int)std::max(kSegLds, (size_t)kXattnLds));
   dec_head_kernel<BIG><<<grid, kNT, layer_lds(g), s>>>(g);
   JANUS_LAUNCH_CHECK();
 }

@@ -329,6 +329,9 @@ struct DecodeStep : LaneBuffers {
   const float *pos_emb, *fin_g, *fin_b;
   const bool fused_ln, ln_fuse, embed_ln, lnp2, lnp3, lnp_fin, rln2, rln3, persist, layerk, xfuse;
   const DecodeRules& R;
+  // the vocabulary projection's and the selectors' arguments: all but the position hold for the call
+  const LogitsArgs logits = logits_args();
+  const SelectArgs select = select_args();
 
   DecodeStep(janus_whisper* w_, const DecodePlan& plan, const LaneBuffers& buf, const BeamState& beam, hipStream_t s_)
       : LaneBuffers(buf), w(w_), P(plan), bst(beam), s(s_), d(w_->cfg.d_model), H(w_->cfg.n_heads),
@@ -343,6 +346,33 @@ struct DecodeStep : LaneBuffers {
         persist(plan.persist >= 1), layerk(plan.persist >= 2), xfuse(plan.persist >= 3), R(plan.R) {}
 
   template <class... Args> GemmArgs dgargs(Args&&... args) const { return janus::dgargs(P, args...); }
+  LogitsArgs logits_args() const {
+    LogitsArgs g;
+    g.A = a; g.lda = d; g.W = w->tok16.as<_Float16>(); g.K = d; g.V = V; g.B = B; g.R = R;
+    if (P.dec_i8) { g.Wq = w->tokq.as<int8_t>(); g.wscale = w->toks.as<float>(); }
+    g.smask = smask; g.rules = rules; g.parts = parts;
+    if (lnp_fin) g.lnx = x;
+    g.ldx = d; g.ln_g = fin_g; g.ln_b = fin_b; g.max_blocks = P.lg_cap;
+    if (P.sampling) g.seeds = seed;
+    if (P.row_temps) g.row_inv_temp = itemp;
+    if (P.beam_k) g.tops = btop;
+    g.hist = hist; g.rep_pen = P.rep_pen;
+    return g;
+  }
+  SelectArgs select_args() const {
+    SelectArgs g;
+    g.parts = parts; g.nblk = P.nblk; g.R = R; g.rules = rules; g.tokens = tokens; g.ld = maxlen;
+    g.done = done; g.sum_lp = sum_lp; g.n_tok = n_tokens; g.plen = prompt; g.nsp = nsp; g.roff = roff;
+    return g;
+  }
+  // the cross-attention launchers' arguments that hold for every layer and position
+  XattnArgs xargs(int nsplit) const {
+    XattnArgs xa;
+    xa.qk = xqk; xa.enc = enc; xa.encq = encq; xa.escale = encs;
+    xa.B = B; xa.Te = Te; xa.D = d; xa.H = H; xa.nsplit = nsplit;
+    xa.part_c = xpc; xa.part_ml = xpml; xa.out = xc;
+    return xa;
+  }
   SkinnyLnArgs lnargs(const float* g, const float* bta, const _Float16* W, const float* bias,
                       void* C, int64_t ldc, int N, _Float16* kcp, _Float16* vcp, int pos) const {
     SkinnyLnArgs p;
@@ -453,9 +483,11 @@ struct DecodeStep : LaneBuffers {
     const DecSegArgs g = seg_args(l, pos);
     if (!layerk) dec_seg_a_launch(g, seg_grid, s);
     else if (l == 0) dec_head_launch(head_args(pos), seg_grid, s);
-    if (!xfuse)  // (persistent 3: the cross-attention ran as the head / layer kernel's last phase)
-      xattn_launch(g.xqk, enc, B, Te, d, H, 1, xpc, xpml, xc,
-                   s, true, nullptr, 0, xrev && (l & 1));
+    if (!xfuse) {  // (persistent 3: the cross-attention ran as the head / layer kernel's last phase)
+      XattnArgs xa = xargs(1);
+      xa.rev = xrev && (l & 1);
+      xattn_launch(xa, s);
+    }
     if (layerk && l + 1 < nl) {
       DecLayer& N = w->dec[l + 1];
       const DecSegNext nx{N.wo.as<_Float16>(), N.bo, N.ln2g, N.ln2b, N.wqk.as<_Float16>(), N.bqk.as<float>()};
@@ -482,23 +514,25 @@ struct DecodeStep : LaneBuffers {
     }
     // o_h = c_h Wv_h^T + bv_h (block-diagonal over heads), then x += o Wo^T + bo; the
     // split merge and the value projection in one launch (cvp) where supported
+    XattnArgs xa = xargs(xsplit);
+    xa.combine = !cvp;
     if (xgroups && P.wide) {
       const int nm = P.n_main >= 0 ? P.n_main : ngroups;
-      xattn_rows_launch(xqk, enc, Te, d, H, xsplit, xpc, xpml, s,
-                        xgroups, nm, grp_rows);
-      if (ngroups > nm)
-        xattn_rows_launch(xqk, enc, Te, d, H, xsplit, xpc, xpml, s,
-                          xgroups + 8 * nm, ngroups - nm, P.rem_rows);
+      xa.groups = xgroups; xa.ngroups = nm; xa.rows_per_group = grp_rows;
+      xattn_rows_launch(xa, s);
+      if (ngroups > nm) {
+        xa.groups = xgroups + 8 * nm; xa.ngroups = ngroups - nm; xa.rows_per_group = P.rem_rows;
+        xattn_rows_launch(xa, s);
+      }
       if (!cvp) xattn_combine_launch(xpc, xpml, xsplit, B, H, d, xc, s);
-    } else if (xgroups)
-      xattn_group_launch(xqk, enc, Te, d, H, xsplit, xpc, xpml, s,
-                         xgroups, ngroups, grp_rows);
-    else if (encq)   // the int8 encoder output (one row, PAIR blocks or one split)
-      xattn_i8_launch(xqk, encq, encs, B, Te, d, H, xsplit, xpc, xpml, xc, s,
-                      !cvp, xpairs, npairs);
-    else
-      xattn_launch(xqk, enc, B, Te, d, H, xsplit, xpc, xpml, xc, s,
-                   !cvp, xpairs, npairs);
+    } else if (xgroups) {
+      xa.groups = xgroups; xa.ngroups = ngroups; xa.rows_per_group = grp_rows;
+      xattn_group_launch(xa, s);
+    } else {
+      xa.pairs = xpairs; xa.npairs = npairs;
+      if (encq) xattn_i8_launch(xa, s);   // the int8 encoder output (one row, PAIR blocks or one split)
+      else xattn_launch(xa, s);
+    }
     if (cvp) {
       xattn_combine_vproj_launch(xpc, xpml, xsplit, B, H, d,
                                  L.wv_c.as<_Float16>(), L.bv_c, o, d, s);
@@ -549,37 +583,28 @@ struct DecodeStep : LaneBuffers {
   // the final LayerNorm, the vocabulary projection's partials, then the selection: the beam
   // step, the select + embed of the next position, or the plain select
   void tail(int pos) const {
-    const int nblk = P.nblk, nwin = P.nwin;
     if (!ln_fuse && !lnp_fin && !layerk) layernorm_launch(x, fin_g, fin_b, a, B, d, 1e-5f, s);
     // history rules: the token at pos into the rows' bit sets, one launch more per position
     if (hist) history_rules_launch(tokens, maxlen, pos, prompt, P.ngram, V, logits_row_group(d), hist, B, s);
-    logits_partial_launch(a, d, w->tok16.as<_Float16>(), d, V, B, R, smask,
-                          rules, parts, s,
-                          lnp_fin ? x : nullptr, d, fin_g, fin_b, P.lg_cap,
-                          P.sampling ? seed : nullptr, pos,
-                          P.row_temps ? itemp : nullptr,
-                          P.beam_k ? btop : nullptr, hist, P.rep_pen,
-                          P.dec_i8 ? w->tokq.as<int8_t>() : nullptr, P.dec_i8 ? w->toks.as<float>() : nullptr);
+    LogitsArgs lg = logits;
+    lg.pos = pos;
+    logits_partial_launch(lg, s);
+    SelectArgs sel = select;
+    sel.pos = pos;
     if (P.beam_k) {
-      beam_step_launch(parts, btop, nblk, R, rules,
-                       tokens, maxlen, pos, done, sum_lp, n_tokens, prompt,
-                       nsp, bst, nwin, s);
+      beam_step_launch(sel, btop, bst, P.nwin, s);
       // the children's K / V rows of positions 0 .. pos follow their parents
       if (pos + 1 < maxlen - 1)
-        beam_reorder_launch(kcache, vcache, nl, nwin, P.beam_k, NC, d, pos,
+        beam_reorder_launch(kcache, vcache, nl, P.nwin, P.beam_k, NC, d, pos,
                             bst.parent, bst.moved, s);
       return;
     }
     if (P.fuse_se && pos + 1 < maxlen - 1)
-      select_embed_launch(parts, nblk, R, rules, tokens,
-                          maxlen, pos, done, sum_lp, n_tokens, B, s, prompt,
-                          nsp, w->tok16.as<_Float16>(), pos_emb, d, x,
+      select_embed_launch(sel, B, s, w->tok16.as<_Float16>(), pos_emb, d, x,
                           fused_ln ? lnp : nullptr, w->dec[0].ln1g, w->dec[0].ln1b,
-                          (ln_fuse || (embed_ln && !layerk)) ? a : nullptr, roff);
+                          (ln_fuse || (embed_ln && !layerk)) ? a : nullptr);
     else
-      select_partials_launch(parts, nblk, R, rules, tokens,
-                             maxlen, pos, done, sum_lp, n_tokens, B, s, prompt,
-                             nsp, roff);
+      select_partials_launch(sel, B, s);
   }
 
   // the embedding and every layer of position pos: the residual rows x before the final

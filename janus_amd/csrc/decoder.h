@@ -85,21 +85,35 @@ int logits_partial_blocks(int V, int K, int max_blocks = 256);
 // rows of A one block holds in LDS (the weights are read once per group of that many rows):
 // 64 up to K = 768, 48 at K = 1024, 32 at K = 1280
 int logits_row_group(int K);
-// lnx: A = LayerNorm(lnx) (fp32 [B][K], eps 1e-5) computed in-block instead of read
-void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K, int V, int B,
-                           const DecodeRules& R, const uint8_t* smask, const RowRules* rules,
-                           LogitPart* parts, hipStream_t s,
-                           const float* lnx = nullptr, int ldx = 0, const float* ln_g = nullptr,
-                           const float* ln_b = nullptr, int max_blocks = 256,
-                           const uint32_t* seeds = nullptr, int pos = 0,
-                           const float* row_inv_temp = nullptr, BeamTop* tops = nullptr,
-                           const uint32_t* hist = nullptr, float rep_pen = 1.f,
-                           const int8_t* Wq = nullptr, const float* wscale = nullptr);
-// Wq / wscale (nullable; greedy, sampling and the history rules, no beam partials, no lnx): the
-// int8 table [V][K] and its row scales replace W: logit = wscale[v] * sum_k A[k] * fp16(Wq[v][k])
-// hist (nullable; greedy and sampling, no beam partials): the rows' history words
-// (history_rules_launch) — a penalised column's logit is scaled by rep_pen (> 0) before the
-// filter, a banned column fails it; the raw statistics stay unpenalised
+// The kernel form follows from the fields set: R.inv_temp > 0 samples, tops the beam partials,
+// hist the history rules, Wq the int8 table.
+struct LogitsArgs {
+  const _Float16* A = nullptr; int lda = 0;   // [B][K] fp16 rows
+  const _Float16* W = nullptr;                // [V][K] fp16 table (null with Wq)
+  // Wq / wscale (nullable; greedy, sampling and the history rules, no beam partials, no lnx): the
+  // int8 table [V][K] and its row scales replace W: logit = wscale[v] * sum_k A[k] * fp16(Wq[v][k])
+  const int8_t* Wq = nullptr; const float* wscale = nullptr;
+  int K = 0, V = 0, B = 0;
+  DecodeRules R{};
+  const uint8_t* smask = nullptr;             // [V] suppressed tokens
+  const RowRules* rules = nullptr;            // [B]
+  LogitPart* parts = nullptr;                 // [B][nblk]
+  // lnx: A = LayerNorm(lnx) (fp32 [B][K], eps 1e-5) computed in-block instead of read
+  const float* lnx = nullptr; int ldx = 0; const float* ln_g = nullptr; const float* ln_b = nullptr;
+  int max_blocks = 256;
+  // R.inv_temp > 0: seeds [B] (device) per-row noise seeds, pos = the position whose logits
+  // these are (the sampled token goes to pos + 1); row_inv_temp [B] (device, nullable): row
+  // b samples at 1 / row_inv_temp[b] instead of R.inv_temp (several temperatures in one call)
+  const uint32_t* seeds = nullptr; int pos = 0; const float* row_inv_temp = nullptr;
+  // tops (nullable, greedy only; [B][nblk]): the beam instantiation — each partial also
+  // carries its block's best kBeamTop allowed entries (BeamTop)
+  BeamTop* tops = nullptr;
+  // hist (nullable; greedy and sampling, no beam partials): the rows' history words
+  // (history_rules_launch) — a penalised column's logit is scaled by rep_pen (> 0) before the
+  // filter, a banned column fails it; the raw statistics stay unpenalised
+  const uint32_t* hist = nullptr; float rep_pen = 1.f;
+};
+void logits_partial_launch(const LogitsArgs& a, hipStream_t s);
 // The history words: uint32 [groups of logits_row_group(K) rows][(V + 15) / 16 tiles][rows of
 // the group], bits 0-15 penalised / 16-31 banned columns of the tile. history_words: their
 // count for B rows (zeroed by the caller before a call's first position).
@@ -108,28 +122,29 @@ size_t history_words(int V, int K, int B);
 // at the same pos): tokens [B][ld], plen [B] prompt lengths, n = no_repeat_ngram_size
 void history_rules_launch(const int32_t* tokens, int ld, int pos, const int32_t* plen, int n, int V,
                           int rg, uint32_t* hist, int B, hipStream_t s);
-// tops (nullable, greedy only; [B][nblk]): the beam instantiation — each partial also
-// carries its block's best kBeamTop allowed entries (BeamTop)
-// R.inv_temp > 0: seeds [B] (device) per-row noise seeds, pos = the position whose logits
-// these are (the sampled token goes to pos + 1); row_inv_temp [B] (device, nullable): row
-// b samples at 1 / row_inv_temp[b] instead of R.inv_temp (several temperatures in one call)
-// plen [B] (device, nullable = all rows sample from pos + 1 >= 1): rows with pos + 1 <
-// plen[b] are still inside their own prompt and keep the forced token. At the step with
-// pos + 1 + R.target_back == plen[b] (target_back 0: the row's first sampled step; > 0: a
-// prompt position, where nothing else is touched) nsp[b] (nullable) gets the raw softmax
-// probability of DecodeRules::target (Whisper's no_speech_prob).
-void select_partials_launch(const LogitPart* parts, int nblk, const DecodeRules& R,
-                            RowRules* rules, int32_t* tokens, int ld, int pos, int32_t* done,
-                            float* sum_lp, int32_t* n_tok, int B, hipStream_t s,
-                            const int32_t* plen = nullptr, float* nsp = nullptr,
-                            const int32_t* roff = nullptr);
+// What the selectors (select_partials_launch, select_embed_launch, beam_step_launch) share: a
+// position's partials, the rules and the rows' state.
+struct SelectArgs {
+  const LogitPart* parts = nullptr; int nblk = 0;   // [rows][nblk]
+  DecodeRules R{};
+  RowRules* rules = nullptr;                        // [rows], rewritten for the next step
+  int32_t* tokens = nullptr; int ld = 0;            // [rows][ld]
+  int pos = 0;                                      // the selected token goes to pos + 1
+  int32_t* done = nullptr; float* sum_lp = nullptr; int32_t* n_tok = nullptr;   // [rows]
+  // plen [B] (device, nullable = all rows sample from pos + 1 >= 1): rows with pos + 1 <
+  // plen[b] are still inside their own prompt and keep the forced token. At the step with
+  // pos + 1 + R.target_back == plen[b] (target_back 0: the row's first sampled step; > 0: a
+  // prompt position, where nothing else is touched) nsp[b] (nullable) gets the raw softmax
+  // probability of DecodeRules::target (Whisper's no_speech_prob).
+  const int32_t* plen = nullptr; float* nsp = nullptr;
+  // per-row position offsets (staggered rows; embed_launch above). Not the beam step.
+  const int32_t* roff = nullptr;
+};
+void select_partials_launch(const SelectArgs& a, int B, hipStream_t s);
 // select_partials_launch at pos followed by embed_launch at pos + 1, in one launch
-void select_embed_launch(const LogitPart* parts, int nblk, const DecodeRules& R, RowRules* rules,
-                         int32_t* tokens, int ld, int pos, int32_t* done, float* sum_lp,
-                         int32_t* n_tok, int B, hipStream_t s, const int32_t* plen, float* nsp,
-                         const _Float16* tok_emb, const float* pos_emb, int d, float* x,
-                         float2* part, const float* ln_g, const float* ln_b, _Float16* ln_out,
-                         const int32_t* roff = nullptr);
+void select_embed_launch(const SelectArgs& a, int B, hipStream_t s, const _Float16* tok_emb,
+                         const float* pos_emb, int d, float* x, float2* part, const float* ln_g,
+                         const float* ln_b, _Float16* ln_out);
 void build_mask_launch(const int32_t* list, int n, uint8_t* mask, int V, hipStream_t s);
 // out [B][V] = sample_gumbel(noise_base(seeds[b], pos), t)
 void sample_gumbel_launch(const uint32_t* seeds, int B, int pos, int V, float* out, hipStream_t s);
@@ -153,10 +168,7 @@ void beam_init_launch(const BeamState& st, int W, hipStream_t s);
 // descending, then beam, then token), the walk (eot candidates finish, the others become the
 // next live beams), the children's tokens / scores / rule states, the finished list and
 // the done flags. Rows inside their prompt keep the forced token with identity parents.
-void beam_step_launch(const LogitPart* parts, const BeamTop* tops, int nblk, const DecodeRules& R,
-                      RowRules* rules, int32_t* tokens, int ld, int pos, int32_t* done,
-                      float* sum_lp, int32_t* n_tok, const int32_t* plen, float* nsp,
-                      const BeamState& st, int W, hipStream_t s);
+void beam_step_launch(const SelectArgs& a, const BeamTop* tops, const BeamState& st, int W, hipStream_t s);
 // The self-attention caches follow the parents: row i of a window takes positions 0 .. pos
 // of row parent[i], in place (a block loads its slab of every row of the window, then
 // stores). kc / vc: [layers][W * k][n_ctx][d] fp16.

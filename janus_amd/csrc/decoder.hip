@@ -9,6 +9,7 @@
 // chosen token's log-probability (avg_logprob).
 #include <cfloat>
 #include <cstdlib>
+#include <utility>
 #ifdef JANUS_DEBUG_ASSERT
 #include <cassert>
 #endif
@@ -370,8 +371,26 @@ void rules_init_launch(RowRules* rules, int B, hipStream_t s) {
 // waves per logits block (16 waves — about one tile per wave — measured 4x slower:
 // 114.7 vs 28.8 us per launch)
 constexpr int lg_waves(int /*K*/) { return 8; }
-constexpr int kLgMt1024 = 3;   // m-tiles per row group at K = 1024 (logits_partial_kernel: 48 rows)
-int logits_row_group(int K) { return K == 1024 ? 16 * kLgMt1024 : K > 768 ? 32 : 64; }
+// The widths the projection is built for: K = d_model and MT, the 16-row m-tiles of A per row
+// group (why 3 at K = 1024 and 2 at K = 1280: at logits_partial_kernel below). The k-steps,
+// the row group, the LDS size and the kernel table all derive from a row of this list.
+struct LgWidth {
+  int K, MT;
+  constexpr int nks() const { return K / 32; }
+  constexpr int rows() const { return 16 * MT; }
+  // A [rows][K + 16] fp16, the waves' patches [waves][rows][17] f32, the rows' rules
+  constexpr size_t lds() const {
+    return (size_t)rows() * (K + 16) * 2 + (size_t)lg_waves(K) * rows() * 17 * 4 + 64 * sizeof(RowRules);
+  }
+};
+constexpr LgWidth kLgWidths[] = {{384, 4}, {512, 4}, {768, 4}, {1024, 3}, {1280, 2}};
+constexpr const LgWidth* lg_width(int K) {
+  for (const LgWidth& w : kLgWidths)
+    if (w.K == K) return &w;
+  return nullptr;
+}
+// (a width without a kernel sizes its history words as before: 32 rows past 768, else 64)
+int logits_row_group(int K) { return lg_width(K) ? lg_width(K)->rows() : K > 768 ? 32 : 64; }
 int logits_partial_blocks(int V, int K, int max_blocks) {
   const int cap = max_blocks > 0 ? max_blocks : 256;  // one per CU of a whole MI355X
   return std::max(1, std::min(cap, ((V + 15) / 16 + lg_waves(K) - 1) / lg_waves(K)));
@@ -807,71 +826,82 @@ __global__ __launch_bounds__(lg_waves(NKS * 32) * 64) void logits_partial_kernel
 }
 #undef LG_LOAD
 
-// the int8-table forms of logits_partial_kernel by K (one function type: same parameters)
-template <bool SAMPLE, bool HIST>
-static auto lg_w8_kernel(int K) {
-  return K == 384   ? logits_partial_kernel<12, 1, SAMPLE, false, 4, HIST, true>
-         : K == 512 ? logits_partial_kernel<16, 1, SAMPLE, false, 4, HIST, true>
-         : K == 768 ? logits_partial_kernel<24, 1, SAMPLE, false, 4, HIST, true>
-         : K == 1024 ? logits_partial_kernel<32, 1, SAMPLE, false, kLgMt1024, HIST, true>
-                     : logits_partial_kernel<40, 1, SAMPLE, false, 2, HIST, true>;
+// The projection's kernel by its key (width, SAMPLE, BEAM, HIST, W8). Every instantiation has
+// the same parameters, so one function type; each travels with its own LDS opt-in.
+using LgKernel = LdsKernel<decltype(logits_partial_kernel<12, 1, false>)>;
+
+// The forms built: the beam partials are greedy, on the fp16 table, without history rules and
+// laid out for 64-row groups (the kernel's static_asserts); every other combination exists.
+constexpr bool lg_built(LgWidth w, bool sample, bool beam, bool hist, bool w8) {
+  return !beam || (w.MT == 4 && !sample && !hist && !w8);
 }
 
-void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K, int V, int B,
-                           const DecodeRules& R, const uint8_t* smask, const RowRules* rules,
-                           LogitPart* parts, hipStream_t s, const float* lnx, int ldx,
-                           const float* ln_g, const float* ln_b, int max_blocks,
-                           const uint32_t* seeds, int pos, const float* row_inv_temp, BeamTop* tops,
-                           const uint32_t* hist, float rep_pen, const int8_t* Wq, const float* wscale) {
-  JANUS_CHECK(!tops || !(R.inv_temp > 0.f), "logits: the beam partials are greedy only");
-  JANUS_CHECK(!Wq || (wscale && !tops && !lnx && ((uintptr_t)Wq & 7) == 0),
+template <int WI, bool SAMPLE, bool BEAM, bool HIST, bool W8>
+constexpr LgKernel lg_select() {
+  constexpr LgWidth w = kLgWidths[WI];
+  if constexpr (lg_built(w, SAMPLE, BEAM, HIST, W8))
+    return lds_kernel<logits_partial_kernel<w.nks(), 1, SAMPLE, BEAM, w.MT, HIST, W8>>();
+  else
+    return {nullptr, nullptr};
+}
+// From run-time flags to template arguments, one flag per step: lg_select<WI>(s, b, h, q) calls
+// lg_select<WI, s>(b, h, q), ... until no flag is left and the overload above, which takes all
+// four as template arguments and none as parameters, is the only one that matches.
+template <int WI, bool... Fs, class... Rest>
+constexpr LgKernel lg_select(bool flag, Rest... rest) {
+  return flag ? lg_select<WI, Fs..., true>(rest...) : lg_select<WI, Fs..., false>(rest...);
+}
+
+// (the row of kLgWidths with this K, whichever rows the list holds; no row: no kernel)
+template <size_t... WI>
+constexpr LgKernel lg_kernel(int K, bool sample, bool beam, bool hist, bool w8, std::index_sequence<WI...>) {
+  LgKernel k{nullptr, nullptr};
+  ((kLgWidths[WI].K == K ? (void)(k = lg_select<(int)WI>(sample, beam, hist, w8)) : (void)0), ...);
+  return k;
+}
+constexpr LgKernel lg_kernel(int K, bool sample, bool beam, bool hist, bool w8) {
+  return lg_kernel(K, sample, beam, hist, w8, std::make_index_sequence<sizeof(kLgWidths) / sizeof(kLgWidths[0])>{});
+}
+
+// the table holds exactly the forms the launcher has always had: counted by part of the key
+constexpr int lg_count(int k_lo, int k_hi, int beam, int hist, int w8) {   // (-1: either)
+  int n = 0;
+  for (const LgWidth& w : kLgWidths)
+    for (int f = 0; f < 16; ++f) {
+      const bool s = f & 1, b = f & 2, h = f & 4, q = f & 8;
+      if (w.K < k_lo || w.K > k_hi || (beam >= 0 && b != (beam != 0)) || (hist >= 0 && h != (hist != 0)) ||
+          (w8 >= 0 && q != (w8 != 0)))
+        continue;
+      n += lg_kernel(w.K, s, b, h, q).fn != nullptr;
+    }
+  return n;
+}
+static_assert(lg_count(384, 768, -1, 0, 0) == 9, "3 widths x {greedy, sample, beam}");
+static_assert(lg_count(1024, 1280, -1, 0, 0) == 4, "1024 and 1280 x {greedy, sample}");
+static_assert(lg_count(384, 1280, -1, 1, 0) == 10, "5 widths x {greedy, sample} with HIST");
+static_assert(lg_count(384, 1280, -1, -1, 1) == 20, "5 x 2 x 2 with W8");
+static_assert(lg_count(384, 1280, -1, -1, -1) == 43, "the forms of logits_partial_kernel");
+
+void logits_partial_launch(const LogitsArgs& a, hipStream_t s) {
+  const DecodeRules& R = a.R;
+  const int K = a.K, V = a.V, B = a.B;
+  JANUS_CHECK(!a.tops || !(R.inv_temp > 0.f), "logits: the beam partials are greedy only");
+  JANUS_CHECK(!a.Wq || (a.wscale && !a.tops && !a.lnx && ((uintptr_t)a.Wq & 7) == 0),
               "logits: the int8 table needs its row scales and has no beam partials and no LayerNorm prologue");
-  JANUS_CHECK(!hist || (!tops && rep_pen > 0.f), "logits: history rules need a penalty > 0 and no beam partials");
-  JANUS_CHECK(K == 384 || K == 512 || K == 768 || K == 1024 || K == 1280,
-              "logits: K (d_model) must be 384, 512, 768, 1024 or 1280");
+  JANUS_CHECK(!a.hist || (!a.tops && a.rep_pen > 0.f), "logits: history rules need a penalty > 0 and no beam partials");
+  const LgWidth* w = lg_width(K);
+  JANUS_CHECK(w != nullptr, "logits: K (d_model) must be 384, 512, 768, 1024 or 1280");
   // K = 1024 / 1280: 48- / 32-row groups (64 rows of A do not fit a CU's LDS), greedy and sampling only
-  const bool k1024 = K == 1024, k1280 = K == 1280;
-  const int rg = logits_row_group(K);
-  JANUS_CHECK(!(k1024 || k1280) || (!tops && !lnx),
+  JANUS_CHECK(w->MT == 4 || (!a.tops && !a.lnx),
               "logits: K = 1024 / 1280 has no beam partials and no LayerNorm prologue");
   const bool sample = R.inv_temp > 0.f;
-  JANUS_CHECK(!sample || seeds, "logits: sampling needs per-row seeds");
+  JANUS_CHECK(!sample || a.seeds, "logits: sampling needs per-row seeds");
+  const LgKernel kern = lg_kernel(K, sample, a.tops != nullptr, a.hist != nullptr, a.Wq != nullptr);
+  JANUS_CHECK(kern.fn != nullptr, "logits: no kernel of this form");   // (the refusals above leave none)
+  kern.allow(160 * 1024);
   const int ntiles = (V + 15) / 16;
-  const int nw = lg_waves(K);
-  const size_t lds = (size_t)rg * (K + 16) * 2 + (size_t)nw * rg * 17 * 4 + 64 * sizeof(RowRules);
-  auto kern = tops ? (K == 384 ? logits_partial_kernel<12, 1, false, true> : K == 512 ? logits_partial_kernel<16, 1, false, true>
-                                                                        : logits_partial_kernel<24, 1, false, true>)
-              : sample ? (K == 384 ? logits_partial_kernel<12, 1, true> : K == 512 ? logits_partial_kernel<16, 1, true>
-                                                                          : logits_partial_kernel<24, 1, true>)
-                       : (K == 384 ? logits_partial_kernel<12, 1, false> : K == 512 ? logits_partial_kernel<16, 1, false>
-                                                                           : logits_partial_kernel<24, 1, false>);
-  if (k1280) kern = sample ? logits_partial_kernel<40, 1, true, false, 2> : logits_partial_kernel<40, 1, false, false, 2>;
-  if (k1024) kern = sample ? logits_partial_kernel<32, 1, true, false, kLgMt1024> : logits_partial_kernel<32, 1, false, false, kLgMt1024>;
-  if (hist) {
-    kern = sample ? (K == 384 ? logits_partial_kernel<12, 1, true, false, 4, true> : K == 512 ? logits_partial_kernel<16, 1, true, false, 4, true>
-                                                                               : logits_partial_kernel<24, 1, true, false, 4, true>)
-                  : (K == 384 ? logits_partial_kernel<12, 1, false, false, 4, true> : K == 512 ? logits_partial_kernel<16, 1, false, false, 4, true>
-                                                                                : logits_partial_kernel<24, 1, false, false, 4, true>);
-    if (k1280) kern = sample ? logits_partial_kernel<40, 1, true, false, 2, true> : logits_partial_kernel<40, 1, false, false, 2, true>;
-    if (k1024) kern = sample ? logits_partial_kernel<32, 1, true, false, kLgMt1024, true> : logits_partial_kernel<32, 1, false, false, kLgMt1024, true>;
-  }
-  int ai8 = -1;
-  if (Wq) {   // the int8 table's forms: greedy / sampling, with and without the history rules
-    W = reinterpret_cast<const _Float16*>(Wq);
-    kern = hist ? (sample ? lg_w8_kernel<true, true>(K) : lg_w8_kernel<false, true>(K))
-                : (sample ? lg_w8_kernel<true, false>(K) : lg_w8_kernel<false, false>(K));
-    ai8 = 23 + 4 * (K == 384 ? 0 : K == 512 ? 1 : K == 768 ? 2 : K == 1024 ? 3 : 4) + 2 * (int)sample + (hist ? 1 : 0);
-  }
-  static bool attr[23 + 20] = {};
-  const int ai = ai8 >= 0 ? ai8 : k1024 ? 19 + (int)sample + (hist ? 2 : 0)
-                 : hist ? 11 + (K == 384 ? 0 : K == 512 ? 1 : K == 768 ? 2 : 3) + (sample ? 4 : 0)
-                      : k1280 ? 9 + (int)sample : (K == 384 ? 0 : K == 512 ? 1 : 2) + (tops ? 6 : sample ? 3 : 0);
-  if (!attr[ai]) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024));
-    attr[ai] = true;
-  }
-  const int grid = logits_partial_blocks(V, K, max_blocks);
+  const int nw = lg_waves(K), rg = w->rows();
+  const int grid = logits_partial_blocks(V, K, a.max_blocks);
   // Tile rotation: waves take tiles t, t + stride, ...; the first ntiles % stride waves get
   // one tile more and set the kernel's length. The special tiles (eot / no_timestamps /
   // timestamps at the top of the vocabulary, and the blank token's tile) run the general
@@ -888,10 +918,14 @@ void logits_partial_launch(const _Float16* A, int lda, const _Float16* W, int K,
     if (rem > 0 && nspec > 0 && rem + nspec + (R.blank >= 0 ? 1 + R.blank / 16 : 0) <= stride)
       rot = ((s0 - rem) % ntiles + ntiles) % ntiles;
   }
+  // the int8 forms read their table through the fp16 table's parameter
+  const _Float16* table = a.Wq ? reinterpret_cast<const _Float16*>(a.Wq) : a.W;
   // 64 (K = 1024: 48, K = 1280: 32) rows per row group (blockIdx.y), every group in one launch
-  kern<<<dim3(grid, (B + rg - 1) / rg), nw * 64, lds, s>>>(A, lda, W, V, B, R, smask, rules, parts, ntiles, lnx, ldx,
-                                                      ln_g, ln_b, rot, seeds, pos,
-                                                      sample ? row_inv_temp : nullptr, tops, hist, rep_pen, wscale);
+  auto* fn = kern.fn;
+  fn<<<dim3(grid, (B + rg - 1) / rg), nw * 64, w->lds(), s>>>(a.A, a.lda, table, V, B, R, a.smask, a.rules, a.parts,
+                                                            ntiles, a.lnx, a.ldx, a.ln_g, a.ln_b, rot, a.seeds,
+                                                            a.pos, sample ? a.row_inv_temp : nullptr, a.tops,
+                                                            a.hist, a.rep_pen, a.wscale);
   JANUS_LAUNCH_CHECK();
 }
 
@@ -1041,26 +1075,20 @@ __global__ __launch_bounds__(256) void select_embed_kernel(
   embed_row(tok_emb, pos_emb, s_tok, blockIdx.x, pb + 1, d, x, part, ln_g, ln_b, ln_out);
 }
 
-void select_embed_launch(const LogitPart* parts, int nblk, const DecodeRules& R, RowRules* rules,
-                         int32_t* tokens, int ld, int pos, int32_t* done, float* sum_lp,
-                         int32_t* n_tok, int B, hipStream_t s, const int32_t* plen, float* nsp,
-                         const _Float16* tok_emb, const float* pos_emb, int d, float* x,
-                         float2* part, const float* ln_g, const float* ln_b, _Float16* ln_out,
-                         const int32_t* roff) {
+void select_embed_launch(const SelectArgs& a, int B, hipStream_t s, const _Float16* tok_emb,
+                         const float* pos_emb, int d, float* x, float2* part, const float* ln_g,
+                         const float* ln_b, _Float16* ln_out) {
   JANUS_CHECK(d % 16 == 0, "embed: d % 16 != 0");
   JANUS_CHECK(!ln_out || d <= 512, "embed: fused LayerNorm needs d <= 512");
-  select_embed_kernel<<<B, 256, 0, s>>>(parts, nblk, R, rules, tokens, ld, pos, done, sum_lp, n_tok,
-                                        plen, nsp, tok_emb, pos_emb, d, x, part, ln_g, ln_b, ln_out,
-                                        roff);
+  select_embed_kernel<<<B, 256, 0, s>>>(a.parts, a.nblk, a.R, a.rules, a.tokens, a.ld, a.pos, a.done, a.sum_lp,
+                                        a.n_tok, a.plen, a.nsp, tok_emb, pos_emb, d, x, part, ln_g, ln_b,
+                                        ln_out, a.roff);
   JANUS_LAUNCH_CHECK();
 }
 
-void select_partials_launch(const LogitPart* parts, int nblk, const DecodeRules& R,
-                            RowRules* rules, int32_t* tokens, int ld, int pos, int32_t* done,
-                            float* sum_lp, int32_t* n_tok, int B, hipStream_t s,
-                            const int32_t* plen, float* nsp, const int32_t* roff) {
-  select_partials_kernel<<<B, 256, 0, s>>>(parts, nblk, R, rules, tokens, ld, pos, done, sum_lp,
-                                           n_tok, plen, nsp, roff);
+void select_partials_launch(const SelectArgs& a, int B, hipStream_t s) {
+  select_partials_kernel<<<B, 256, 0, s>>>(a.parts, a.nblk, a.R, a.rules, a.tokens, a.ld, a.pos, a.done,
+                                           a.sum_lp, a.n_tok, a.plen, a.nsp, a.roff);
   JANUS_LAUNCH_CHECK();
 }
 

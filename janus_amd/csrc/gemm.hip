@@ -558,12 +558,7 @@ static void skinny_go(const SkinnyArgs& p, dim3 grid, hipStream_t s) {
   size_t lds = 0;
   if constexpr (AM == AM_LNX) {
     lds = (size_t)16 * MTB * frag_pitch(p.K) * 2;
-    static bool attr = false;
-    if (!attr) {
-      JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    100 * 1024));
-      attr = true;
-    }
+    allow_dynamic_lds<gemm_skinny_kernel<EPI, AM, MTB, false, W8>>(100 * 1024);  // (kern, of this branch)
   }
   kern<<<grid, 1024, lds, s>>>(p);
 }
@@ -594,13 +589,8 @@ static void launch_skinny_t(int epi, const SkinnyArgs& p, hipStream_t s) {
   if constexpr ((AM == AM_F16 || AM == AM_LNX) && !W8) {
     if (epi == EPI_F16 && p.N > 2048 && p.K <= kSkWaves * 32 && p.a_group_cols == 0 && p.M <= 64) {
       if constexpr (AM == AM_LNX) {
-        auto kern = gemm_skinny2_kernel<true>;
-        static bool attr = false;
-        if (!attr) {
-          JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        88 * 1024));
-          attr = true;
-        }
+        constexpr auto kern = gemm_skinny2_kernel<true>;
+        allow_dynamic_lds<kern>(88 * 1024);
         kern<<<(p.N + 31) / 32, 1024, (size_t)64 * frag_pitch(p.K) * 2, s>>>(p);
       } else {
         gemm_skinny2_kernel<false><<<(p.N + 31) / 32, 1024, 0, s>>>(p);
@@ -850,14 +840,9 @@ __global__ __launch_bounds__(NW * 64) void resid_ln_kernel(ResidLnArgs p) {
 
 template <int NW, int K>
 static void resid_ln_go(const ResidLnArgs& p, hipStream_t s) {
-  auto kern = resid_ln_kernel<NW, K>;
+  constexpr auto kern = resid_ln_kernel<NW, K>;
   const size_t lds = (size_t)16 * frag_pitch(p.K) * 2 + (size_t)(16 + 2) * 32 * NW * 4;
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<kern>(160 * 1024);
   kern<<<(p.M + 15) / 16, NW * 64, lds, s>>>(p);
 }
 

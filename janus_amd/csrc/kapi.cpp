@@ -244,9 +244,11 @@ extern "C" int janus_cross_attention_f16(const uint16_t* qk, const uint16_t* enc
                                          int Te, int D, int H, int nsplit, float* part_c,
                                          float* part_ml, uint16_t* out, void* stream) {
   return guarded([&] {
-    xattn_launch(reinterpret_cast<const _Float16*>(qk), reinterpret_cast<const _Float16*>(enc),
-                 batch, Te, D, H, nsplit, part_c, part_ml, reinterpret_cast<_Float16*>(out),
-                 (hipStream_t)stream);
+    XattnArgs a;
+    a.qk = reinterpret_cast<const _Float16*>(qk); a.enc = reinterpret_cast<const _Float16*>(enc);
+    a.B = batch; a.Te = Te; a.D = D; a.H = H; a.nsplit = nsplit;
+    a.part_c = part_c; a.part_ml = part_ml; a.out = reinterpret_cast<_Float16*>(out);
+    xattn_launch(a, (hipStream_t)stream);
   });
 }
 
@@ -282,6 +284,16 @@ static DecodeRules beam_rules(int eot, int suppress_blank, int blank, int ts_beg
   return R;
 }
 
+// the vocabulary projection's arguments as the kernel-level entry points give them
+static LogitsArgs logits_args(const uint16_t* A, int K, int V, int batch, const DecodeRules& R, const uint8_t* smask,
+                              const int32_t* row_rules, int max_blocks, void* parts) {
+  LogitsArgs a;
+  a.A = reinterpret_cast<const _Float16*>(A); a.lda = K; a.K = K; a.V = V; a.B = batch; a.R = R;
+  a.smask = smask; a.rules = reinterpret_cast<const RowRules*>(row_rules);
+  a.parts = static_cast<LogitPart*>(parts); a.max_blocks = max_blocks;
+  return a;
+}
+
 extern "C" int janus_beam_partial_blocks(int V, int K, int max_blocks) {
   return logits_partial_blocks(V, K, max_blocks);
 }
@@ -298,10 +310,10 @@ extern "C" int janus_beam_logits_topk_f16(const uint16_t* A, const uint16_t* W, 
     static_assert(sizeof(RowRules) == 32 && sizeof(LogitPart) == 56 && sizeof(BeamTop) == 256, "ABI sizes");
     const DecodeRules R = beam_rules(eot, suppress_blank, blank, ts_begin, no_timestamps, max_initial_ts);
     const int nblk = logits_partial_blocks(V, K, max_blocks);
-    logits_partial_launch(reinterpret_cast<const _Float16*>(A), K, reinterpret_cast<const _Float16*>(W), K, V,
-                          batch, R, smask, reinterpret_cast<const RowRules*>(row_rules),
-                          static_cast<LogitPart*>(parts), (hipStream_t)stream, nullptr, 0, nullptr, nullptr,
-                          max_blocks, nullptr, 0, nullptr, static_cast<BeamTop*>(tops));
+    LogitsArgs a = logits_args(A, K, V, batch, R, smask, row_rules, max_blocks, parts);
+    a.W = reinterpret_cast<const _Float16*>(W);
+    a.tops = static_cast<BeamTop*>(tops);
+    logits_partial_launch(a, (hipStream_t)stream);
     beam_rowtop_launch(static_cast<const BeamTop*>(tops), nblk, batch, n2k, all_v, all_i, ts_v, ts_i,
                        (hipStream_t)stream);
   });
@@ -322,10 +334,10 @@ extern "C" int janus_logits_partial_f16(const uint16_t* A, const uint16_t* W, in
     DecodeRules R = beam_rules(eot, suppress_blank, blank, ts_begin, no_timestamps, max_initial_ts);
     R.target = target;
     R.inv_temp = inv_temp > 0.f ? inv_temp : 0.f;
-    logits_partial_launch(reinterpret_cast<const _Float16*>(A), K, reinterpret_cast<const _Float16*>(W), K, V,
-                          batch, R, smask, reinterpret_cast<const RowRules*>(row_rules),
-                          static_cast<LogitPart*>(parts), (hipStream_t)stream, nullptr, 0, nullptr, nullptr,
-                          max_blocks, seeds, pos, nullptr, nullptr);
+    LogitsArgs a = logits_args(A, K, V, batch, R, smask, row_rules, max_blocks, parts);
+    a.W = reinterpret_cast<const _Float16*>(W);
+    a.seeds = seeds; a.pos = pos;
+    logits_partial_launch(a, (hipStream_t)stream);
   });
 }
 
@@ -358,10 +370,11 @@ extern "C" int janus_logits_partial_hist_f16(const uint16_t* A, const uint16_t* 
     DecodeRules R = beam_rules(eot, suppress_blank, blank, ts_begin, no_timestamps, max_initial_ts);
     R.target = target;
     R.inv_temp = inv_temp > 0.f ? inv_temp : 0.f;
-    logits_partial_launch(reinterpret_cast<const _Float16*>(A), K, reinterpret_cast<const _Float16*>(W), K, V,
-                          batch, R, smask, reinterpret_cast<const RowRules*>(row_rules),
-                          static_cast<LogitPart*>(parts), (hipStream_t)stream, nullptr, 0, nullptr, nullptr,
-                          max_blocks, seeds, pos, nullptr, nullptr, hist, repetition_penalty);
+    LogitsArgs a = logits_args(A, K, V, batch, R, smask, row_rules, max_blocks, parts);
+    a.W = reinterpret_cast<const _Float16*>(W);
+    a.seeds = seeds; a.pos = pos;
+    a.hist = hist; a.rep_pen = repetition_penalty;
+    logits_partial_launch(a, (hipStream_t)stream);
   });
 }
 
@@ -372,10 +385,11 @@ static int logits_partial_w8(const uint16_t* A, const int8_t* q, const float* sc
   return guarded([&] {
     JANUS_CHECK(A && q && scale && smask && row_rules && parts, "null argument");
     JANUS_CHECK(batch >= 1 && batch <= kSkinnyMaxRows, "logits_partial: 1 <= batch <= 512");
-    logits_partial_launch(reinterpret_cast<const _Float16*>(A), K, nullptr, K, V, batch, R, smask,
-                          reinterpret_cast<const RowRules*>(row_rules), static_cast<LogitPart*>(parts),
-                          (hipStream_t)stream, nullptr, 0, nullptr, nullptr, max_blocks, seeds, pos, nullptr, nullptr,
-                          hist, repetition_penalty, q, scale);
+    LogitsArgs a = logits_args(A, K, V, batch, R, smask, row_rules, max_blocks, parts);
+    a.Wq = q; a.wscale = scale;
+    a.seeds = seeds; a.pos = pos;
+    a.hist = hist; a.rep_pen = repetition_penalty;
+    logits_partial_launch(a, (hipStream_t)stream);
   });
 }
 
@@ -425,9 +439,11 @@ extern "C" int janus_beam_step(const void* parts, const void* tops, int nblk, in
     st.k = beam_size; st.length_penalty = 1.0f;
     st.nlive = nlive; st.nfin = nfin; st.wdone = wdone; st.moved = moved; st.parent = parent;
     st.fin_tok = fin_tok; st.fin_s = fin_s; st.fin_n = fin_n;
-    beam_step_launch(static_cast<const LogitPart*>(parts), static_cast<const BeamTop*>(tops), nblk, R,
-                     reinterpret_cast<RowRules*>(row_rules), tokens, ld, pos, done, sum_lp, n_tok, plen,
-                     nullptr, st, n_windows, (hipStream_t)stream);
+    SelectArgs a;
+    a.parts = static_cast<const LogitPart*>(parts); a.nblk = nblk; a.R = R;
+    a.rules = reinterpret_cast<RowRules*>(row_rules); a.tokens = tokens; a.ld = ld; a.pos = pos;
+    a.done = done; a.sum_lp = sum_lp; a.n_tok = n_tok; a.plen = plen;
+    beam_step_launch(a, static_cast<const BeamTop*>(tops), st, n_windows, (hipStream_t)stream);
   });
 }
 

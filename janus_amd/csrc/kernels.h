@@ -148,34 +148,47 @@ bool xattn_supported(int D, int H);
 int xattn_split_count(int Te, int requested);
 void xattn_absorb(const float* wq, const float* bq, const float* wk, int D, int H,
                   _Float16* wqk, float* bqk, hipStream_t s);
-// pairs (nullable, device int4 [npairs] = {b0, b1, e, -}): decoder rows b0 and b1 (b1 < 0:
-// none) attend to encoder row e of enc, read once for both (H <= 8, D <= 512); without it
-// row b reads enc row b.
-void xattn_launch(const _Float16* qk, const _Float16* enc, int B, int Te, int D, int H,
-                  int nsplit, float* part_c, float* part_ml, _Float16* out, hipStream_t s,
-                  bool combine = true, const int4* pairs = nullptr, int npairs = 0, bool rev = false);
+// What the four cross-attention launchers take; each reads the fields of its own form.
+struct XattnArgs {
+  const _Float16* qk = nullptr;     // [B][H*D]
+  const _Float16* enc = nullptr;    // [n][Te][D] fp16 encoder rows (every launcher but xattn_i8_launch)
+  const int8_t* encq = nullptr;     // xattn_i8_launch: int8 [n][Te][D] ...
+  const float* escale = nullptr;    // ... and its row scales f32 [n][Te]
+  int B = 0, Te = 0, D = 0, H = 0;
+  int nsplit = 1;                   // key splits, 1 .. 63
+  float* part_c = nullptr;          // [B][nsplit][H][D] f32
+  float* part_ml = nullptr;         // [B][nsplit][H][2] f32
+  _Float16* out = nullptr;          // c [B][H*D] (one-row launchers with combine)
+  // one-row launchers: merge the splits into out (false: the caller merges, e.g. with
+  // xattn_combine_vproj_launch). One split with the merge requested runs the form that writes
+  // out itself (D <= 512).
+  bool combine = true;
+  // pairs (nullable, device int4 [npairs] = {b0, b1, e, -}): decoder rows b0 and b1 (b1 < 0:
+  // none) attend to encoder row e of enc, read once for both (H <= 8, D <= 512); without it
+  // row b reads enc row b.
+  const int4* pairs = nullptr; int npairs = 0;
+  bool rev = false;                 // fp16, D = 512, one split: walk the key chunks last to first
+  // xattn_group_launch / xattn_rows_launch: groups [device] int [ngroups][8] = {e, row_0 ..
+  // row_5 (-1: none), -}, rows_per_group = the rows of the largest group
+  const int* groups = nullptr; int ngroups = 0, rows_per_group = 0;
+};
+void xattn_launch(const XattnArgs& a, hipStream_t s);
 // xattn_launch over the row-quantised encoder output (quant_rows_i8_launch's q and scale of
 // the fp16 rows): encq int8 [n][Te][D], escale f32 [n][Te]. The kernel sees E'[t][j] =
 // fp16(float(q[t][j]) * s[t]) (fp32 product, rounded once) where xattn_launch sees E; the
 // split form at every width, PAIR and the one-split form up to D = 512.
-void xattn_i8_launch(const _Float16* qk, const int8_t* encq, const float* escale, int B, int Te, int D, int H,
-                     int nsplit, float* part_c, float* part_ml, _Float16* out, hipStream_t s,
-                     bool combine = true, const int4* pairs = nullptr, int npairs = 0);
+void xattn_i8_launch(const XattnArgs& a, hipStream_t s);
 // Groups of <= 6 decoder rows sharing an encoder row, one block per (split, group):
 // groups [device] int [ngroups][8] = {e, row_0 .. row_5 (-1: none), -}; partials as
 // xattn_launch(combine = false) writes them (merged by xattn_combine_vproj_launch).
-void xattn_group_launch(const _Float16* qk, const _Float16* enc, int Te, int D, int H, int nsplit,
-                        float* part_c, float* part_ml, hipStream_t s, const int* groups, int ngroups,
-                        int rows_per_group);
+void xattn_group_launch(const XattnArgs& a, hipStream_t s);
 // The 12-head family (D = 768): blocks of <= xattn_rows_max(D, H) = 4 decoder rows sharing an
 // encoder row, 12 heads per row packed into 1..3 MFMA m-tiles; groups as above (row_4, row_5
 // unused). Writes the partials the one-row xattn_launch(combine = false) writes, bit for
 // bit; xattn_combine_launch merges them as xattn_launch(combine = true) does.
 bool xattn_rows_supported(int D, int H);
 int xattn_rows_max(int D, int H);
-void xattn_rows_launch(const _Float16* qk, const _Float16* enc, int Te, int D, int H, int nsplit,
-                       float* part_c, float* part_ml, hipStream_t s, const int* groups, int ngroups,
-                       int rows_per_group);
+void xattn_rows_launch(const XattnArgs& a, hipStream_t s);
 void xattn_combine_launch(const float* part_c, const float* part_ml, int nsplit, int B, int H, int D,
                           _Float16* out, hipStream_t s);
 // The split merge of xattn_launch(..., combine = false) fused with the per-head value

@@ -329,13 +329,8 @@ template <int C, int K, int D, int BM, int NW>
 static void narrow_cfg(const ResUnitArgs& a, hipStream_t s) {
   using G = NarrowGeo<C, K, D, BM, NW>;
   static_assert(G::LDS <= 160 * 1024, "LDS");
-  auto kern = resunit_kernel<C, K, D, BM, NW>;
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)G::LDS));
-    attr = true;
-  }
+  constexpr auto kern = resunit_kernel<C, K, D, BM, NW>;
+  allow_dynamic_lds<kern>((int)G::LDS);
   const int tiles_per_utt = (a.T + BM - 1) / BM;
   const int n_tiles = tiles_per_utt * a.B;
   const int per_cu = std::max(1, std::min(4, (int)((160 * 1024) / G::LDS)));

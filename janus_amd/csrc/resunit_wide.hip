@@ -471,13 +471,8 @@ template <int C, int KC, int DC>
 static void wide_go(const ResUnitArgs& a, hipStream_t s) {
   using G = WideGeo<C>;
   static_assert(G::LDS <= 160 * 1024, "LDS");
-  auto kern = resunit_wide_kernel<C, KC, DC>;
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)G::LDS));
-    attr = true;
-  }
+  constexpr auto kern = resunit_wide_kernel<C, KC, DC>;
+  allow_dynamic_lds<kern>((int)G::LDS);
   const int tiles_per_utt = (a.T + G::BM - 1) / G::BM;
   long long* prof = nullptr;
 #ifdef JANUS_PHASE_PROF
@@ -787,13 +782,8 @@ template <int C, int KC, int DC>
 static void lds_go(const ResUnitArgs& a, hipStream_t s) {
   using G = LdsGeo<C>;
   static_assert(G::LDS <= 160 * 1024, "LDS");
-  auto kern = resunit_wide_lds_kernel<C, KC, DC>;
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)G::LDS));
-    attr = true;
-  }
+  constexpr auto kern = resunit_wide_lds_kernel<C, KC, DC>;
+  allow_dynamic_lds<kern>((int)G::LDS);
   const int tiles_per_utt = (a.T + G::BM - 1) / G::BM;
   kern<<<(unsigned)(tiles_per_utt * a.B), G::NT, G::LDS, s>>>(a, tiles_per_utt);
   JANUS_LAUNCH_CHECK();

@@ -188,12 +188,7 @@ __global__ __launch_bounds__(kPostThreads) void conv_post_kernel(const _Float16*
 void conv_post_launch(const _Float16* x, int B, int T, const float* w, float bias, float* wav,
                       int16_t* pcm, hipStream_t s, int pre_silu, float* pre_tanh) {
   if (B <= 0 || T <= 0) return;
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)conv_post_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPostLds));
-    attr = true;
-  }
+  allow_dynamic_lds<conv_post_kernel>((int)kPostLds);
   conv_post_kernel<<<dim3((T + kPostT - 1) / kPostT, B), kPostThreads, kPostLds, s>>>(
       x, T, w, bias, wav, pcm, pre_silu, pre_tanh);
   JANUS_LAUNCH_CHECK();

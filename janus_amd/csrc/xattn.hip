@@ -287,42 +287,40 @@ __global__ __launch_bounds__(CH * 8, 1) void xattn_group_kernel(
   }
 }
 
-template <int D, int CH, int NMT>
-static void xattn_group_cfg(const _Float16* qk, const _Float16* enc, int Te, int H, int nsplit,
-                            float* part_c, float* part_ml, hipStream_t s, const int* groups, int ngroups) {
+// keys of one split: whole CH-key chunks, the same for every launcher that writes partials
+static int xattn_keys_per_split(int Te, int CH, int nsplit) {
   const int chunks = (Te + CH - 1) / CH;
-  const int kps = (chunks + nsplit - 1) / nsplit * CH;
+  return (chunks + nsplit - 1) / nsplit * CH;
+}
+
+template <int D, int CH, int NMT>
+static void xattn_group_cfg(const XattnArgs& a, hipStream_t s) {
   using G = XGeo<D, CH>;
   constexpr int R16 = 16 * NMT;
   constexpr int QR = NMT >= 3 ? 1 : NMT;
   constexpr size_t lds = (size_t)(CH * G::QP + R16 * G::PP) * 2 + (size_t)2 * R16 * CH * 4 + R16 * 4 +
                          (size_t)(NMT - QR) * 16 * D * 2;
-  auto kern = xattn_group_kernel<D, CH, NMT>;
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
-  kern<<<dim3(nsplit, ngroups), CH * 8, lds, s>>>(qk, enc, Te, H, kps, part_c, part_ml, groups);
+  constexpr auto kern = xattn_group_kernel<D, CH, NMT>;
+  allow_dynamic_lds<kern>(160 * 1024);
+  kern<<<dim3(a.nsplit, a.ngroups), CH * 8, lds, s>>>(a.qk, a.enc, a.Te, a.H, xattn_keys_per_split(a.Te, CH, a.nsplit),
+                                                      a.part_c, a.part_ml, a.groups);
   JANUS_LAUNCH_CHECK();
 }
 
-void xattn_group_launch(const _Float16* qk, const _Float16* enc, int Te, int D, int H, int nsplit,
-                        float* part_c, float* part_ml, hipStream_t s, const int* groups, int ngroups,
-                        int rows_per_group) {
-  JANUS_CHECK(H <= 8 && (D == 384 || D == 512) && H * 64 == D, "xattn groups: H <= 8, D in {384, 512}");
-  JANUS_CHECK(rows_per_group >= 1 && rows_per_group <= 6, "xattn groups: 1..6 rows per group");
-  JANUS_CHECK(nsplit >= 1 && nsplit <= 63, "xattn: 1..63 key splits");
-  if (ngroups <= 0 || Te <= 0) return;
-  const int nmt = (rows_per_group + 1) / 2;
-  if (D == 512) {
-    if (nmt == 1) xattn_group_cfg<512, 64, 1>(qk, enc, Te, H, nsplit, part_c, part_ml, s, groups, ngroups);
-    else if (nmt == 2) xattn_group_cfg<512, 64, 2>(qk, enc, Te, H, nsplit, part_c, part_ml, s, groups, ngroups);
-    else xattn_group_cfg<512, 64, 3>(qk, enc, Te, H, nsplit, part_c, part_ml, s, groups, ngroups);
+void xattn_group_launch(const XattnArgs& a, hipStream_t s) {
+  JANUS_CHECK(a.H <= 8 && (a.D == 384 || a.D == 512) && a.H * 64 == a.D, "xattn groups: H <= 8, D in {384, 512}");
+  JANUS_CHECK(a.rows_per_group >= 1 && a.rows_per_group <= 6, "xattn groups: 1..6 rows per group");
+  JANUS_CHECK(a.nsplit >= 1 && a.nsplit <= 63, "xattn: 1..63 key splits");
+  if (a.ngroups <= 0 || a.Te <= 0) return;
+  const int nmt = (a.rows_per_group + 1) / 2;
+  if (a.D == 512) {
+    if (nmt == 1) xattn_group_cfg<512, 64, 1>(a, s);
+    else if (nmt == 2) xattn_group_cfg<512, 64, 2>(a, s);
+    else xattn_group_cfg<512, 64, 3>(a, s);
   } else {
-    if (nmt == 1) xattn_group_cfg<384, 64, 1>(qk, enc, Te, H, nsplit, part_c, part_ml, s, groups, ngroups);
-    else if (nmt == 2) xattn_group_cfg<384, 64, 2>(qk, enc, Te, H, nsplit, part_c, part_ml, s, groups, ngroups);
-    else xattn_group_cfg<384, 64, 3>(qk, enc, Te, H, nsplit, part_c, part_ml, s, groups, ngroups);
+    if (nmt == 1) xattn_group_cfg<384, 64, 1>(a, s);
+    else if (nmt == 2) xattn_group_cfg<384, 64, 2>(a, s);
+    else xattn_group_cfg<384, 64, 3>(a, s);
   }
 }
 
@@ -534,23 +532,17 @@ __global__ __launch_bounds__(CH * 8, NMT == 1 ? 2 : 1) void xattn_rows_kernel(
 }
 
 template <int D, int CH, int NMT, int HR>
-static void xattn_rows_cfg(const _Float16* qk, const _Float16* enc, int Te, int nsplit, float* part_c,
-                           float* part_ml, hipStream_t s, const int* groups, int ngroups) {
-  const int chunks = (Te + CH - 1) / CH;
-  const int kps = (chunks + nsplit - 1) / nsplit * CH;  // xattn_cfg's split geometry
+static void xattn_rows_cfg(const XattnArgs& a, hipStream_t s) {
   using G = XGeo<D, CH>;
   constexpr int R16 = 16 * NMT;
   constexpr int QR = NMT >= 3 ? 1 : NMT;
   constexpr size_t lds = (size_t)(CH * G::QP + R16 * G::PP) * 2 + (size_t)2 * R16 * CH * 4 + R16 * 4 +
                          (size_t)(NMT - QR) * 16 * G::QP * 2;
   static_assert(lds <= 160 * 1024, "xattn rows: LDS per block");
-  auto kern = xattn_rows_kernel<D, CH, NMT, HR>;
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
-  kern<<<dim3(nsplit, ngroups), CH * 8, lds, s>>>(qk, enc, Te, kps, part_c, part_ml, groups);
+  constexpr auto kern = xattn_rows_kernel<D, CH, NMT, HR>;
+  allow_dynamic_lds<kern>(160 * 1024);
+  kern<<<dim3(a.nsplit, a.ngroups), CH * 8, lds, s>>>(a.qk, a.enc, a.Te, xattn_keys_per_split(a.Te, CH, a.nsplit),
+                                                      a.part_c, a.part_ml, a.groups);
   JANUS_LAUNCH_CHECK();
 }
 
@@ -558,17 +550,15 @@ bool xattn_rows_supported(int D, int H) { return D == 768 && H == 12; }
 
 int xattn_rows_max(int D, int H) { return xattn_rows_supported(D, H) ? 4 : 0; }
 
-void xattn_rows_launch(const _Float16* qk, const _Float16* enc, int Te, int D, int H, int nsplit,
-                       float* part_c, float* part_ml, hipStream_t s, const int* groups, int ngroups,
-                       int rows_per_group) {
-  JANUS_CHECK(xattn_rows_supported(D, H), "xattn rows: D = 768, H = 12 (the 8-head models take PAIR blocks)");
-  JANUS_CHECK(rows_per_group >= 1 && rows_per_group <= 4, "xattn rows: 1..4 rows per block at 12 heads");
-  JANUS_CHECK(nsplit >= 1 && nsplit <= 63, "xattn: 1..63 key splits");
-  if (ngroups <= 0 || Te <= 0) return;
+void xattn_rows_launch(const XattnArgs& a, hipStream_t s) {
+  JANUS_CHECK(xattn_rows_supported(a.D, a.H), "xattn rows: D = 768, H = 12 (the 8-head models take PAIR blocks)");
+  JANUS_CHECK(a.rows_per_group >= 1 && a.rows_per_group <= 4, "xattn rows: 1..4 rows per block at 12 heads");
+  JANUS_CHECK(a.nsplit >= 1 && a.nsplit <= 63, "xattn: 1..63 key splits");
+  if (a.ngroups <= 0 || a.Te <= 0) return;
   // m-tiles by the largest block: 1 row = 12 of 16 MFMA rows, 2 = 24 of 32, 3..4 = 36 / 48 of 48
-  if (rows_per_group == 1) xattn_rows_cfg<768, 32, 1, 12>(qk, enc, Te, nsplit, part_c, part_ml, s, groups, ngroups);
-  else if (rows_per_group == 2) xattn_rows_cfg<768, 32, 2, 12>(qk, enc, Te, nsplit, part_c, part_ml, s, groups, ngroups);
-  else xattn_rows_cfg<768, 32, 3, 12>(qk, enc, Te, nsplit, part_c, part_ml, s, groups, ngroups);
+  if (a.rows_per_group == 1) xattn_rows_cfg<768, 32, 1, 12>(a, s);
+  else if (a.rows_per_group == 2) xattn_rows_cfg<768, 32, 2, 12>(a, s);
+  else xattn_rows_cfg<768, 32, 3, 12>(a, s);
 }
 
 // c[b][h*D + j] = sum_s 2^(m_s - M) C_s[h][j] / sum_s 2^(m_s - M) l_s   (fp16)
@@ -778,37 +768,6 @@ int xattn_split_count(int Te, int requested) {
   return std::max(n, 1);
 }
 
-template <int D, int CH>
-static void xattn_cfg(const _Float16* qk, const _Float16* enc, int B, int Te, int H, int nsplit,
-                      float* part_c, float* part_ml, hipStream_t s, const int4* pairs, int npairs,
-                      _Float16* out = nullptr, bool rev = false) {
-  const int chunks = (Te + CH - 1) / CH;
-  const int kps = (chunks + nsplit - 1) / nsplit * CH;
-  const bool direct = out != nullptr;
-  // one split: D = 512 loads whole rows (ROWLD) with one chunk in flight — two in flight
-  // (two register sets of 8 rows: 158 VGPRs, one block per CU) measured slower at 256 rows
-  // (decoder 1539 vs 1444 us per position in the staggered step,
-  // profiles/r06_xattn_ab.txt); the fragment-pattern loads keep two chunks in flight (PF2)
-  constexpr bool row = D == 512 && CH == 64;
-  decltype(&xattn_kernel<D, CH, false>) kern;
-  if (direct) {
-    if constexpr (row) kern = xattn_kernel<D, CH, false, true, false, true>;
-    else kern = xattn_kernel<D, CH, false, true, true>;
-  } else {
-    kern = pairs ? xattn_kernel<D, CH, true> : xattn_kernel<D, CH, false>;
-  }
-  const int ai = direct ? 2 : pairs != nullptr;
-  static bool attr[3] = {false, false, false};
-  if (!attr[ai]) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024));
-    attr[ai] = true;
-  }
-  kern<<<dim3(nsplit, pairs ? npairs : B), CH * 8, XGeo<D, CH>::LDS, s>>>(qk, enc, Te, H, kps, part_c,
-                                                                         part_ml, pairs, out, rev ? 1 : 0);
-  JANUS_LAUNCH_CHECK();
-}
-
 static void xattn_combine_rows(const float* part_c, const float* part_ml, int nsplit, int B, int H, int D,
                                _Float16* out, hipStream_t s) {
   if (H <= 16) xattn_combine_kernel<16><<<B, 256, 0, s>>>(part_c, part_ml, nsplit, H, D, out);
@@ -833,127 +792,112 @@ bool xattn_supported(int D, int H) {
   return H * 64 == D && H <= kXCombHeads && (D == 384 || D == 512 || D == 768 || D == 1024 || D == 1280);
 }
 
-// D = 1280, 20 heads: two head groups of 10 per (split, row) in grid.z, 32-key chunks. The E
-// chunk is 32 x 1296 halves = 83 KB (88.6 KB with P and the scores): one block per CU, 4 waves.
-// Each group reads the encoder row (E is read twice per decoder row); one 32-row block would
-// hold Q (2 m-tiles x 20 k-steps), E (20) and C (2 x 20 tiles) in ~400 registers per lane.
-static void xattn_1280(const _Float16* qk, const _Float16* enc, int B, int Te, int H, int nsplit,
-                       float* part_c, float* part_ml, hipStream_t s) {
-  constexpr int D = 1280, CH = 32, HG = 10;
-  const int chunks = (Te + CH - 1) / CH;
-  const int kps = (chunks + nsplit - 1) / nsplit * CH;
-  auto kern = xattn_kernel<D, CH, false, false, false, false, HG>;
-  static_assert(XGeo<D, CH>::LDS <= 160 * 1024, "xattn 1280: LDS per block");
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
-  kern<<<dim3(nsplit, B, (H + HG - 1) / HG), CH * 8, XGeo<D, CH>::LDS, s>>>(qk, enc, Te, H, kps, part_c, part_ml,
-                                                                            nullptr, nullptr, 0);
-  JANUS_LAUNCH_CHECK();
-}
-
+// ------------------------------------------- the one-row launch: fp16 and int8 encoder output
+// The geometry of a width: CH keys per chunk (a block is CH * 8 threads), HG heads per block
+// in grid.z (0: every head of the row in one block).
+// 384 / 512: 64-key chunks (8 waves). 768: 32-key chunks.
 // D = 1024, 16 heads: the heads fill the block's one 16-row MFMA tile, so one block per (split,
 // row) holds them all (no head groups: the encoder row is read once per decoder row), 32-key
 // chunks. The E chunk is 32 x 1040 halves = 66 560 B (72 256 B with P and the scores). Only the
 // split form is built: no PAIR, no DIRECT.
-static void xattn_1024(const _Float16* qk, const _Float16* enc, int B, int Te, int H, int nsplit,
-                       float* part_c, float* part_ml, hipStream_t s) {
-  constexpr int D = 1024, CH = 32;
-  const int chunks = (Te + CH - 1) / CH;
-  const int kps = (chunks + nsplit - 1) / nsplit * CH;
-  auto kern = xattn_kernel<D, CH, false>;
-  static_assert(XGeo<D, CH>::LDS <= 160 * 1024, "xattn 1024: LDS per block");
-  static bool attr = false;
-  if (!attr) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
+// D = 1280, 20 heads: two head groups of 10 per (split, row) in grid.z, 32-key chunks. The E
+// chunk is 32 x 1296 halves = 83 KB (88.6 KB with P and the scores): one block per CU, 4 waves.
+// Each group reads the encoder row (E is read twice per decoder row); one 32-row block would
+// hold Q (2 m-tiles x 20 k-steps), E (20) and C (2 x 20 tiles) in ~400 registers per lane.
+template <int D_, int CH_, int HG_ = 0>
+struct XWidth {
+  static constexpr int D = D_, CH = CH_, HG = HG_;
+};
+
+template <class F>
+static void xattn_by_width(int D, F&& f) {
+  switch (D) {
+    case 384: return f(XWidth<384, 64>{});
+    case 512: return f(XWidth<512, 64>{});
+    case 768: return f(XWidth<768, 32>{});
+    case 1024: return f(XWidth<1024, 32>{});
+    default: return f(XWidth<1280, 32, 10>{});   // (xattn_supported admits no other)
   }
-  kern<<<dim3(nsplit, B), CH * 8, XGeo<D, CH>::LDS, s>>>(qk, enc, Te, H, kps, part_c, part_ml, nullptr, nullptr, 0);
+}
+
+// The form of a one-row launch. PAIR (two decoder rows per encoder row read) and DIRECT (one
+// key split, the kernel writes c itself: no partials, no merge) are built up to D = 512.
+enum XForm { X_SPLIT, X_PAIR, X_DIRECT };
+static XForm xattn_form(const XattnArgs& a) {
+  JANUS_CHECK(!a.pairs || (a.H <= 8 && a.npairs >= 1 && a.D <= 512), "xattn: row pairs need H <= 8, D <= 512");
+  if (a.combine && a.nsplit == 1 && !a.pairs && a.D <= 512) return X_DIRECT;
+  return a.pairs ? X_PAIR : X_SPLIT;
+}
+
+template <class W>
+static LdsKernel<decltype(xattn_kernel<W::D, W::CH>)> xattn_f16_form(XForm form) {
+  constexpr int D = W::D, CH = W::CH;
+  if constexpr (D <= 512) {
+    // one split: D = 512 loads whole rows (ROWLD) with one chunk in flight — two in flight
+    // (two register sets of 8 rows: 158 VGPRs, one block per CU) measured slower at 256 rows
+    // (decoder 1539 vs 1444 us per position in the staggered step,
+    // profiles/r06_xattn_ab.txt); the fragment-pattern loads keep two chunks in flight (PF2)
+    if (form == X_DIRECT) {
+      if constexpr (D == 512) return lds_kernel<xattn_kernel<D, CH, false, true, false, true>>();
+      else return lds_kernel<xattn_kernel<D, CH, false, true, true>>();
+    }
+    if (form == X_PAIR) return lds_kernel<xattn_kernel<D, CH, true>>();
+  }
+  return lds_kernel<xattn_kernel<D, CH, false, false, false, false, W::HG>>();
+}
+
+// (the int8 forms: plain one-deep loads in every form, so DIRECT has no PF2 / ROWLD choice)
+template <class W>
+static LdsKernel<decltype(xattn_i8_kernel<W::D, W::CH>)> xattn_i8_form(XForm form) {
+  constexpr int D = W::D, CH = W::CH;
+  if constexpr (D <= 512) {
+    if (form == X_DIRECT) return lds_kernel<xattn_i8_kernel<D, CH, false, true>>();
+    if (form == X_PAIR) return lds_kernel<xattn_i8_kernel<D, CH, true>>();
+  }
+  return lds_kernel<xattn_i8_kernel<D, CH, false, false, W::HG>>();
+}
+
+template <class W, bool I8>
+static void xattn_cfg(const XattnArgs& a, XForm form, hipStream_t s) {
+  constexpr int D = W::D, CH = W::CH;
+  static_assert(XGeo<D, CH>::LDS <= 160 * 1024, "xattn: LDS per block");
+  constexpr int hg = W::HG ? W::HG : 32;   // (no head groups: every head in one block)
+  const dim3 grid(a.nsplit, form == X_PAIR ? a.npairs : a.B, W::HG ? (a.H + hg - 1) / hg : 1);
+  const int kps = xattn_keys_per_split(a.Te, CH, a.nsplit);
+  _Float16* out = form == X_DIRECT ? a.out : nullptr;
+  if constexpr (I8) {
+    const auto kern = xattn_i8_form<W>(form);
+    kern.allow(160 * 1024);
+    auto* fn = kern.fn;
+    fn<<<grid, CH * 8, XGeo<D, CH>::LDS, s>>>(a.qk, reinterpret_cast<const signed char*>(a.encq), a.escale, a.Te,
+                                              a.H, kps, a.part_c, a.part_ml, a.pairs, out);
+  } else {
+    const auto kern = xattn_f16_form<W>(form);
+    kern.allow(160 * 1024);
+    auto* fn = kern.fn;
+    fn<<<grid, CH * 8, XGeo<D, CH>::LDS, s>>>(a.qk, a.enc, a.Te, a.H, kps, a.part_c, a.part_ml, a.pairs, out,
+                                              form == X_DIRECT && D == 512 && a.rev ? 1 : 0);
+  }
   JANUS_LAUNCH_CHECK();
 }
 
-void xattn_launch(const _Float16* qk, const _Float16* enc, int B, int Te, int D, int H,
-                  int nsplit, float* part_c, float* part_ml, _Float16* out, hipStream_t s,
-                  bool combine, const int4* pairs, int npairs, bool rev) {
-  JANUS_CHECK(xattn_supported(D, H), "xattn: need D = 64 H in {384, 512, 768, 1024, 1280}");
-  if (B <= 0 || Te <= 0) return;
-  JANUS_CHECK(nsplit >= 1 && nsplit <= 63, "xattn: 1..63 key splits");
-  JANUS_CHECK(!pairs || (H <= 8 && npairs >= 1 && D <= 512), "xattn: row pairs need H <= 8, D <= 512");
-  // one key split with the merge requested: the kernel writes c itself (DIRECT), no merge
-  if (combine && nsplit == 1 && !pairs && D <= 512) {
-    if (D == 384) xattn_cfg<384, 64>(qk, enc, B, Te, H, 1, part_c, part_ml, s, nullptr, 0, out);
-    else xattn_cfg<512, 64>(qk, enc, B, Te, H, 1, part_c, part_ml, s, nullptr, 0, out, rev);
-    return;
-  }
-  // 64-key chunks (8 waves); D = 768: 32-key chunks
-  if (D == 384) xattn_cfg<384, 64>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
-  else if (D == 512) xattn_cfg<512, 64>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
-  else if (D == 768) xattn_cfg<768, 32>(qk, enc, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
-  else if (D == 1024) xattn_1024(qk, enc, B, Te, H, nsplit, part_c, part_ml, s);
-  else xattn_1280(qk, enc, B, Te, H, nsplit, part_c, part_ml, s);
-  if (!combine) return;  // the caller merges (xattn_combine_vproj_launch)
-  if (nsplit <= kXCombMax && D <= 512)
-    xattn_combine_wide_kernel<<<dim3(H, B), 128, 0, s>>>(part_c, part_ml, nsplit, H, D, out);
-  else
-    xattn_combine_rows(part_c, part_ml, nsplit, B, H, D, out, s);
-  JANUS_LAUNCH_CHECK();
+template <bool I8>
+static void xattn_one_row(const XattnArgs& a, hipStream_t s) {
+  JANUS_CHECK(xattn_supported(a.D, a.H), "xattn: need D = 64 H in {384, 512, 768, 1024, 1280}");
+  if constexpr (I8) JANUS_CHECK(a.encq && a.escale, "xattn int8: null encoder rows or scales");
+  if (a.B <= 0 || a.Te <= 0) return;
+  JANUS_CHECK(a.nsplit >= 1 && a.nsplit <= 63, "xattn: 1..63 key splits");
+  const XForm form = xattn_form(a);
+  xattn_by_width(a.D, [&](auto w) { xattn_cfg<decltype(w), I8>(a, form, s); });
+  // DIRECT wrote c itself; without combine the caller merges (xattn_combine_vproj_launch)
+  if (form != X_DIRECT && a.combine) xattn_combine_launch(a.part_c, a.part_ml, a.nsplit, a.B, a.H, a.D, a.out, s);
 }
 
-// ------------------------------------------------------------ int8 encoder output
+void xattn_launch(const XattnArgs& a, hipStream_t s) { xattn_one_row<false>(a, s); }
+
 // xattn_launch over the row-quantised encoder output (janus_whisper_set_cross_compute): encq
 // int8 [n][Te][D], escale f32 [n][Te]; the forms the decode call's launch path uses — the split
-// form at every width, PAIR and DIRECT (one split, plain one-deep loads) up to D = 512. The
-// merges are xattn_launch's.
-template <int D, int CH, int HG = 0>
-static void xattn_i8_cfg(const _Float16* qk, const int8_t* encq, const float* escale, int B, int Te, int H,
-                         int nsplit, float* part_c, float* part_ml, hipStream_t s, const int4* pairs,
-                         int npairs, _Float16* out = nullptr) {
-  const int chunks = (Te + CH - 1) / CH;
-  const int kps = (chunks + nsplit - 1) / nsplit * CH;
-  const bool direct = out != nullptr;
-  static_assert(XGeo<D, CH>::LDS <= 160 * 1024, "xattn int8: LDS per block");
-  decltype(&xattn_i8_kernel<D, CH, false, false, HG>) kern;
-  if constexpr (HG != 0 || D > 512) {
-    kern = xattn_i8_kernel<D, CH, false, false, HG>;
-  } else {
-    if (direct) kern = xattn_i8_kernel<D, CH, false, true>;
-    else kern = pairs ? xattn_i8_kernel<D, CH, true> : xattn_i8_kernel<D, CH, false>;
-  }
-  const int ai = direct ? 2 : pairs != nullptr;
-  static bool attr[3] = {false, false, false};
-  if (!attr[ai]) {
-    JANUS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr[ai] = true;
-  }
-  constexpr int hg = HG ? HG : 32;   // (no head groups: every head in one block)
-  const dim3 grid(nsplit, pairs ? npairs : B, HG ? (H + hg - 1) / hg : 1);
-  kern<<<grid, CH * 8, XGeo<D, CH>::LDS, s>>>(qk, reinterpret_cast<const signed char*>(encq), escale, Te, H, kps,
-                                              part_c, part_ml, pairs, out);
-  JANUS_LAUNCH_CHECK();
-}
-
-void xattn_i8_launch(const _Float16* qk, const int8_t* encq, const float* escale, int B, int Te, int D, int H,
-                     int nsplit, float* part_c, float* part_ml, _Float16* out, hipStream_t s, bool combine,
-                     const int4* pairs, int npairs) {
-  JANUS_CHECK(xattn_supported(D, H), "xattn: need D = 64 H in {384, 512, 768, 1024, 1280}");
-  JANUS_CHECK(encq && escale, "xattn int8: null encoder rows or scales");
-  if (B <= 0 || Te <= 0) return;
-  JANUS_CHECK(nsplit >= 1 && nsplit <= 63, "xattn: 1..63 key splits");
-  JANUS_CHECK(!pairs || (H <= 8 && npairs >= 1 && D <= 512), "xattn: row pairs need H <= 8, D <= 512");
-  if (combine && nsplit == 1 && !pairs && D <= 512) {   // DIRECT: the kernel writes c itself
-    if (D == 384) xattn_i8_cfg<384, 64>(qk, encq, escale, B, Te, H, 1, part_c, part_ml, s, nullptr, 0, out);
-    else xattn_i8_cfg<512, 64>(qk, encq, escale, B, Te, H, 1, part_c, part_ml, s, nullptr, 0, out);
-    return;
-  }
-  if (D == 384) xattn_i8_cfg<384, 64>(qk, encq, escale, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
-  else if (D == 512) xattn_i8_cfg<512, 64>(qk, encq, escale, B, Te, H, nsplit, part_c, part_ml, s, pairs, npairs);
-  else if (D == 768) xattn_i8_cfg<768, 32>(qk, encq, escale, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
-  else if (D == 1024) xattn_i8_cfg<1024, 32>(qk, encq, escale, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
-  else xattn_i8_cfg<1280, 32, 10>(qk, encq, escale, B, Te, H, nsplit, part_c, part_ml, s, nullptr, 0);
-  if (!combine) return;  // the caller merges (xattn_combine_vproj_launch)
-  xattn_combine_launch(part_c, part_ml, nsplit, B, H, D, out, s);
-}
+// form at every width, PAIR and DIRECT (one split) up to D = 512. The merges are xattn_launch's.
+void xattn_i8_launch(const XattnArgs& a, hipStream_t s) { xattn_one_row<true>(a, s); }
 
 }  // namespace janus

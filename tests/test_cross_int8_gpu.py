@@ -11,12 +11,13 @@ Each case asserts from the plan that int8 ran, and on which cross-attention form
 Models: decoder_ref.config — two decoder layers, 64 vocabulary entries, 141 encoder keys (two
 64-key chunks plus 13) unless stated; T = 3 positions unless stated.
 
-  1. hidden-state parity   384 / 6 rows 1, 17; 512 / 8 rows 1, 17, 64, 65 at one key split (the
-                           kernel writes the context rows itself, DIRECT) and at 3; 512 / 8 over
+  1. hidden-state parity   384 / 6 rows 1, 17, and 2 rows at one key split; 512 / 8 rows 1, 17, 64,
+                           65 at one key split (at one split the kernel writes the context rows
+                           itself, DIRECT) and at 3; 512 / 8 over
                            1500 keys, 3 rows at 8 splits; 768 / 12, 1024 / 16 and 1280 / 20 (two
                            head groups) rows 1, 17
-  2. shared rows           13 rows over 3 encoder rows (5 + 5 + 3): PAIR blocks in place at 512,
-                           gathered q and s at 768 and 1280
+  2. shared rows           13 rows over 3 encoder rows (5 + 5 + 3): PAIR blocks in place at 384
+                           and 512, gathered q and s at 768 and 1280
   3. edge rows in E        a zero key row, a row whose amax is negative, 16.0 planted in one
                            seeded column of every other key row
   4. the control           on the outlier input hidden(E) and hidden(E') lie more than 4 bounds
@@ -147,6 +148,9 @@ def run_int8(M, name, B, plan_want, **opts):
 # ------------------------------------------------------------ 1. hidden-state parity
 SPLIT = {"call.enc_rows": OWN, "npairs": 0}
 CASES = [(f"384-rows{B}", (384, 6), B, dict(SPLIT, xsplit=3, cvp=1), {}) for B in (1, 17)]
+# (the one-split form at 384 / 6 has no other test)
+CASES.append(("384-rows2-direct", (384, 6), 2, dict(SPLIT, xsplit=1, cvp=0),
+              dict(xattn_splits=1, path_flags=jw.DEC_PATH_NO_CVP)))
 for _B in (1, 17, 64, 65):
     # one key split and no fused merge: the kernel writes the context rows itself (DIRECT)
     CASES.append((f"512-rows{_B}-direct", (512, 8), _B, dict(SPLIT, xsplit=1, cvp=0),
@@ -165,6 +169,7 @@ def test_hidden_parity(models, name, shape, B, plan, opts):
 # ------------------------------------------------------------ 2. shared encoder rows
 PAIRS = [0, 1, 0, 2, 3, 0, 4, -1, 0, 5, 6, 1, 7, 8, 1, 9, -1, 1, 10, 11, 2, 12, -1, 2]
 SHARED = [
+    ("384-pair", (384, 6), dict(npairs=8, pairs=PAIRS, cvp=1, **{"call.enc_rows": IN_PLACE, "call.n_enc": 3}), "in_place"),
     ("512-pair", (512, 8), dict(npairs=8, pairs=PAIRS, cvp=1, **{"call.enc_rows": IN_PLACE, "call.n_enc": 3}), "in_place"),
     ("768-gathered", (768, 12), dict(npairs=0, wide=1, **{"call.enc_rows": GATHERED, "call.n_enc": 13}), "gathered"),
     ("1280-gathered", (1280, 20), dict(npairs=0, wide=1, **{"call.enc_rows": GATHERED, "call.n_enc": 13}), "gathered"),

@@ -4,7 +4,7 @@ table stays in the Infinity Cache) and with 512 MB written before each launch ("
 comes from HBM, as after a 24-layer decoder step). One JSON line on stdout.
 
 The row-group comparison of DESIGN.md §5q (profiles/medium_family_row_group.json): build a
-second library with kLgMt1024 = 2 in csrc/decoder.hip
+second library with MT = 2 in the K = 1024 row of kLgWidths (csrc/decoder.hip; once kLgMt1024)
   make -C janus_amd/csrc OUT=../libjanus_hip_mt2.so OBJDIR=../../build/obj_mt2
 and run this tool in alternating processes, three rounds:
   python tools/logits_projection_time.py; JANUS_LIB=libjanus_hip_mt2.so python tools/logits_projection_time.py"""
