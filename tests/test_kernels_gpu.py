@@ -23,9 +23,13 @@ def rel_err(a, b):
 
 
 @pytest.mark.parametrize("M,N,K", [(300, 200, 64), (64, 1536, 512), (1, 24, 8), (1500, 512, 2048),
-                                   (129, 130, 136), (64, 4096, 512), (20, 2056, 384), (7, 2304, 200)])
+                                   (129, 130, 136), (64, 4096, 512), (20, 2056, 384), (7, 2304, 200),
+                                   (33, 3840, 1280), (64, 1280, 5120), (1, 5120, 1280), (17, 1280, 1280),
+                                   (20, 4096, 1024)])
 @pytest.mark.parametrize("epi", [0, 1, 2, 3])
 def test_gemm(gpu, M, N, K, epi):
+    """M <= 64 is the skinny (decoder) kernel: the last five shapes are the 1280 / 1024 families'
+    projections (QKV, fc2, fc1, out_proj; K = 1280 is 40 k-steps over 16 waves, a ragged split)."""
     g = torch.Generator().manual_seed(M * 7 + N + K + epi)
     A = (torch.randn(M, K, generator=g)).half()
     W = (torch.randn(N, K, generator=g) / math.sqrt(K)).half()
@@ -47,7 +51,8 @@ def test_gemm(gpu, M, N, K, epi):
 
 
 @pytest.mark.parametrize("M,N,K", [(3000, 1536, 512), (256, 512, 512), (4500, 2048, 512),
-                                   (3000, 512, 2048), (257, 256, 64), (300, 256, 128)])
+                                   (3000, 512, 2048), (257, 256, 64), (300, 256, 128),
+                                   (257, 3840, 1280), (300, 1280, 5120)])
 @pytest.mark.parametrize("epi", [0, 1, 2, 3])
 def test_gemm_big(gpu, M, N, K, epi):
     """The encoder-size kernel (janus_gemm_f16 with N % 256 == 0, K % 64 == 0 -> gemm_big:
@@ -133,8 +138,10 @@ def test_gemm_lt(gpu, M, N, K, epi):
 
 
 def test_layernorm(gpu):
+    """333 rows (ragged against any row blocking) at every model width; d > 1024 runs
+    layernorm_kernel<8>."""
     g = torch.Generator().manual_seed(1)
-    for d in (384, 512, 768):
+    for d in (384, 512, 768, 1024, 1280):
         x = torch.randn(333, d, generator=g) * 3 + 1
         gam, bet = torch.randn(d, generator=g), torch.randn(d, generator=g)
         ref = F.layer_norm(x.double(), (d,), gam.double(), bet.double(), 1e-5)
@@ -143,10 +150,10 @@ def test_layernorm(gpu):
         nat.call("janus_layernorm_f16", dx.data_ptr(), dg.data_ptr(), db.data_ptr(),
                  out.data_ptr(), 333, d, 1e-5, stream())
         torch.cuda.synchronize()
-        assert rel_err(out, ref) < 1e-3
+        assert rel_err(out, ref) < 1e-3, d
 
 
-@pytest.mark.parametrize("B,T,H", [(2, 100, 2), (1, 1500, 6), (3, 65, 8)])
+@pytest.mark.parametrize("B,T,H", [(2, 100, 2), (1, 1500, 6), (3, 65, 8), (1, 65, 12), (1, 100, 16), (2, 65, 20)])
 def test_attention(gpu, B, T, H):
     g = torch.Generator().manual_seed(T + H)
     d = H * 64
@@ -288,10 +295,15 @@ def test_cross_attention_absorbed(gpu, B, Te, D, nsplit):
 
 @pytest.mark.parametrize("B,T,H,split", [(3, 1, 8, 0), (2, 37, 6, 0), (64, 448, 8, 0), (2, 512, 8, 0),
                                          (2, 700, 8, 1), (3, 1000, 8, 1),
-                                         (2, 64, 12, 0), (2, 65, 12, 0), (5, 448, 12, 0)])
+                                         (2, 64, 12, 0), (2, 65, 12, 0), (5, 448, 12, 0)]
+                         # NR = 2 .. 7 key rounds of the per-head kernel, both sides of every 64-key round
+                         + [(2, T, 8, 0) for T in (128, 129, 192, 193, 256, 257, 320, 321, 384, 385)]
+                         # 16 and 20 heads (d = 1024, 1280)
+                         + [(3, 200, 16, 0), (2, 448, 16, 0), (3, 65, 20, 0), (2, 448, 20, 0)])
 def test_decode_attention(gpu, B, T, H, split):
     """One query per (b, h) against a KV cache with row stride > d (the decoder's cache
-    layout [B][n_ctx][d]); per-head kernel (T <= 512) and the key-split + combine path."""
+    layout [B][n_ctx][d]); per-head kernel (T <= 512, decode_head_kernel<NR> with NR =
+    ceil(T / 64) rounds of 64 keys) and the key-split + combine path."""
     d, n_ctx = H * 64, max(T, 448) + 5
     g = torch.Generator().manual_seed(B * 100 + T + H)
     q = (torch.randn(B, 3 * d, generator=g)).half()          # q is the first d of a qkv row

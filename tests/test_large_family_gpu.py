@@ -1,12 +1,16 @@
 """The 1280-wide, 20-head family (large-v3, large-v3-turbo, distil-large-v3) on the GPU against
-the unchanged oracle (oracle/whisper.py) and tests/large_family_ref.py. Every test runs the
-cut config — the real width, heads, 128 mel bins and the 51 866-entry vocabulary over 2 encoder
-and 2 decoder layers, synthetic weights (seed 11) — so each takes seconds.
+the unchanged oracle (oracle/whisper.py), tests/large_family_ref.py and tests/decoder_ref.py.
+Every test runs the cut config — the real width, heads, 128 mel bins and the 51 866-entry
+vocabulary over 2 encoder and 2 decoder layers, synthetic weights (seed 11) — a kernel alone, or
+the residual-stream model of tests/test_decoder_hidden_gpu.py at 1280 / 20, so each takes
+seconds.
 
 Tolerances are the project's: 2e-3 (log-mel), ENC_TOL (encoder, relative RMS), NEAR_TIE (a
 free-running decode may leave the oracle's only where the oracle's own top-2 margin is below
-it), the sum_logprob / no_speech_prob bounds of tests/test_small_family_gpu.py and
-DETECT_BOUND of tests/test_multilingual_gpu.py.
+it), the sum_logprob / no_speech_prob bounds of tests/test_small_family_gpu.py,
+DETECT_BOUND of tests/test_multilingual_gpu.py, the cross-attention bound of
+tests/test_kernels_gpu.py (XATTN_TOL = 3e-3, twice that on a single head) and K_BOUND of
+tests/decoder_ref.py (three times the fp16 emulation's own distance from float64).
 
 Seeds, chosen on the CPU oracle alone (W = synthetic_weights(CUT, 11)):
 * greedy rows: encoder seeds 900 .. 904 with the five prompts of greedy_prompts(); the oracle's
@@ -15,12 +19,46 @@ Seeds, chosen on the CPU oracle alone (W = synthetic_weights(CUT, 11)):
   key margins 8.5e-2, 7.7e-2, 1.4e-1, 1.0e-1, 9.3e-2 (10 x NEAR_TIE / T is 3.3e-2);
 * language windows: encoder seeds 930 .. 932, reference top-2 logit gaps 0.78, 0.62, 0.77;
 * seek loop: synth_speech seeds 170 (35 s) and 171 (4 s), first-window language gaps 8.2e-2
-  and 9.6e-2."""
+  and 9.6e-2;
+* residual stream: decoder_ref.config(1280, 20, 141), weights seed 3, inputs seed 5 (the seeds
+  of tests/test_decoder_hidden_gpu.py), one draw of 65 rows x 5 positions and one of 17 x 70.
+
+Measured on the MI355X (printed by the tests, pytest -s).
+
+Residual stream of the default (float16) decode call at 1280 / 20, row / tile, with the
+emulation's own figure on the same rows after the bar (the bound is three times that one):
+  case           x                                        k cache tile        v cache tile
+  rows 1, T 5    5.77e-4 / 8.67e-4 | 5.61e-4 / 9.13e-4    9.19e-4 | 9.19e-4   9.81e-4 | 8.48e-4
+  rows 17, T 5   6.28e-4 / 8.93e-4 | 6.31e-4 / 9.56e-4    1.06e-3 | 9.98e-4   1.07e-3 | 1.08e-3
+  rows 65, T 5   6.28e-4 / 9.95e-4 | 6.31e-4 / 9.91e-4    1.06e-3 | 1.08e-3   1.09e-3 | 1.13e-3
+  rows 17, T 70  6.50e-4 / 1.03e-3 | 6.51e-4 / 1.03e-3    1.25e-3 | 1.19e-3   1.21e-3 | 1.22e-3
+  shared rows    5.72e-4 / 8.67e-4 | 5.53e-4 / 9.13e-4    9.19e-4 | 9.27e-4   9.94e-4 | 9.60e-4
+The path sits at 0.9 - 1.2 times the emulation, as the other widths do. The defect (fc2 bias of
+layer 1 zeroed on columns 1264 .. 1279): reference 4.76e-2, engine 4.77e-2, both 17.4x the
+bound 2.74e-3 at column 1264; the restored engine's worst tile is 8.93e-4 (0.33x).
+
+Cross-attention alone (xattn_kernel<1280, 32, HG = 10> and the 20-head merge), relative error
+overall, then the worst head of group 0 (heads 0 - 9) and of group 1 (10 - 19); the bounds are
+3e-3 and 6e-3:
+  rows  keys  splits   overall   group 0   group 1
+     1  1500       1   2.22e-4   2.73e-4   2.50e-4
+     1  1500       8   2.09e-4   2.33e-4   2.25e-4
+     2  1500       3   2.13e-4   2.43e-4   2.37e-4
+     2   141       1   2.13e-4   2.62e-4   2.66e-4
+    17   141       3   2.13e-4   2.84e-4   2.77e-4
+    17    77       8   2.14e-4   2.88e-4   2.88e-4
+     2    33       1   2.20e-4   2.94e-4   2.69e-4
+     2    32       1   2.19e-4   2.79e-4   2.63e-4
+     1  1500      17   2.05e-4   2.14e-4   2.15e-4"""
+import functools
+import math
+
 import numpy as np
 import pytest
 import torch
 
 import beam_ref
+import decoder_ref as dref
 import large_family_ref as lf
 import multilingual_ref as mr
 from janus_amd import _native as nat
@@ -38,6 +76,7 @@ NEAR_TIE = 2e-3
 ENC_TOL = 1e-3
 NSP_REL = 5e-3
 DETECT_BOUND = 4 * 2.80e-3          # tests/test_multilingual_gpu.py
+XATTN_TOL = 3e-3                    # tests/test_kernels_gpu.py::test_cross_attention_absorbed
 ML = 32
 GREEDY_SEEDS = [900, 901, 902, 903, 904]
 SAMPLE_SEEDS = [3001, 3002, 3003, 3005, 3012]
@@ -449,3 +488,197 @@ def test_second_tier_is_refused_before_gpu_work(cut, gpu):
         eng.decode_beam(enc, beam_size=4, max_length=16)
     with pytest.raises(NotImplementedError, match="word_timestamps"):
         eng.align(enc, [[300, 400]], [3000])
+
+
+# ------------------------------------------------------------------ 9. cross-attention alone
+XATTN_CASES = [(1, 1500, 1), (1, 1500, 8), (2, 1500, 3), (2, 141, 1), (17, 141, 3), (17, 77, 8), (2, 33, 1),
+               (2, 32, 1), (1, 1500, 17)]
+
+
+@pytest.mark.parametrize("B,Te,nsplit", XATTN_CASES, ids=[f"{b}rows-{t}keys-{n}" for b, t, n in XATTN_CASES])
+def test_cross_attention_absorbed_1280(gpu, B, Te, nsplit):
+    """xattn_kernel<1280, 32, .., HG = 10> (two head-group blocks per (split, row) in grid.z, each
+    on 10 of its 16 MFMA rows) and the 20-head merge through janus_cross_attention_f16:
+    softmax_2(qk_h . enc^T) . enc per head against the float64 torch reference of the same fp16
+    operands, XATTN_TOL overall and 2 XATTN_TOL on every one of the 20 heads of every row; the
+    worst head of group 0 (heads 0 - 9) and of group 1 (10 - 19) is printed on its own. At this
+    width one split is the split kernel plus the merge too (no DIRECT form). Key counts 1500 (46
+    chunks of 32 + 28), 141 and 77 (ragged last chunks; 77 keys at 8 splits leaves splits without
+    keys), 33 (one key past a chunk) and 32 (exactly one); 17 splits is more than 16 through
+    xattn_combine_kernel<20>, the only merge at this width. The 17-row cases index two encoder
+    rows by gathered copy, and rows over the same encoder row with the same query must come out
+    bit-identical. The partials are filled with NaN before the call: a slot the merge reads that
+    no block wrote (an empty split, the second group's offset) poisons the output. The entry
+    rejected none of the key counts."""
+    D, H, HG = 1280, 20, 10
+    g = torch.Generator().manual_seed(B * 1000 + Te + D + nsplit)
+    n_enc = min(B, 2)
+    enc_rows = torch.randn(n_enc, Te, D, generator=g).half()
+    idx = [b % n_enc for b in range(B)]
+    enc = enc_rows[idx].contiguous()                      # the gather of shared rows
+    qk = (torch.randn(B, H, D, generator=g) * 0.15).half()
+    if B >= 4:
+        qk[2] = qk[0]                                     # same query, same encoder row (0)
+    s = torch.einsum("bhd,btd->bht", qk.double(), enc.double())
+    p = torch.softmax(s * math.log(2.0), dim=-1)
+    ref = torch.einsum("bht,btd->bhd", p, enc.double()).reshape(B, H * D)
+    dq, de = qk.to(gpu), enc.to(gpu)
+    pc = torch.full((B * nsplit * H * D,), float("nan"), dtype=torch.float32, device=gpu)
+    pml = torch.full((B * nsplit * H * 2,), float("nan"), dtype=torch.float32, device=gpu)
+    out = torch.full((B, H * D), float("nan"), dtype=torch.float16, device=gpu)
+    nat.call("janus_cross_attention_f16", dq.data_ptr(), de.data_ptr(), B, Te, D, H, nsplit,
+             pc.data_ptr(), pml.data_ptr(), out.data_ptr(), nat.stream_ptr())
+    torch.cuda.synchronize()
+    got = out.double().cpu()
+    err = float((got - ref).norm() / ref.norm())
+    heads = (got - ref).view(B, H, D).norm(dim=-1) / ref.view(B, H, D).norm(dim=-1)      # [B][20]
+    g0, g1 = float(heads[:, :HG].max()), float(heads[:, HG:].max())
+    b_, h_ = divmod(int(torch.nan_to_num(heads, nan=float("inf")).argmax()), H)
+    print(f"xattn 1280 / 20: {B} rows, {Te} keys, {nsplit} splits: rel {err:.2e}, worst head of group 0 "
+          f"{g0:.2e}, of group 1 {g1:.2e} (row {b_} head {h_})")
+    assert bool(torch.isfinite(got).all()), f"non-finite output, first at row {b_} head {h_}"
+    assert err < XATTN_TOL, err
+    assert max(g0, g1) < 2 * XATTN_TOL, f"row {b_} head {h_} (group {h_ // HG}): {max(g0, g1):.2e}"
+    if B >= 4:
+        assert torch.equal(out[2], out[0])
+
+
+# ------------------------------------------------------------------ 10. decoder residual stream
+ENC_INDEX = [0] * 5 + [1] * 5 + [2] * 3
+GATHERED = 2                        # call.enc_rows (tests/test_decoder_hidden_gpu.py)
+DEFECT_NAME, DEFECT_COL = "decoder.layers.1.fc2.bias", 1264      # the last of the 80 tiles
+WIDE_PLAN = dict(persist=0, xabs=1, wide=1, npairs=0, ngroups=0, fused_ln=0, ln_fuse=0, rln=0, ln_pro_mask=0,
+                 cvp=0, xsplit=3)
+
+
+@functools.lru_cache(maxsize=None)
+def hidden_case(rows=65, T=5):
+    """tests/test_decoder_hidden_gpu.py's model at 1280 / 20: two decoder layers, 64 vocabulary
+    entries, 141 encoder keys; rows x T positions of forced tokens and their float64 references
+    (exact and emulated), computed once per shape. CPU only."""
+    cfg = dref.config(1280, 20, 141)
+    W = dref.weights(cfg, 3)
+    tokens, enc = dref.inputs(cfg, rows, T, 5)
+    exact = dref.hidden(tokens, enc, W, cfg)
+    emu = dref.hidden(tokens, enc, W, cfg, emulate=True)
+    return cfg, W, tokens, enc, exact, emu
+
+
+@functools.lru_cache(maxsize=None)
+def shared_case():
+    """13 rows over the first 3 encoder rows of hidden_case() (5 + 5 + 3), 3 positions. CPU only."""
+    cfg, W, tokens, enc, _, _ = hidden_case()
+    B, T = len(ENC_INDEX), 3
+    exact = dref.hidden(tokens[:B, :T], enc[:3], W, cfg, enc_index=ENC_INDEX)
+    emu = dref.hidden(tokens[:B, :T], enc[:3], W, cfg, enc_index=ENC_INDEX, emulate=True)
+    return tokens[:B, :T], exact, emu
+
+
+@functools.lru_cache(maxsize=None)
+def defect_case():
+    """17 rows x 3 positions of hidden_case() with fc2's bias of layer 1 zeroed on columns
+    1264 .. 1279: (tokens, clean x, the tile bound, the defective reference's worst column and
+    tile). The reference alone must separate the two by the margin the GPU test asks of the
+    engine — asserted here, on the CPU, before any GPU work."""
+    cfg, W, tokens, enc, exact, emu = hidden_case()
+    B, T = 17, 3
+    rx, ex = exact[0][:B, :T], emu[0][:B, :T]
+    bound = dref.K_BOUND * dref.metrics(ex, rx)[1]
+    bad, _, _ = dref.hidden(tokens[:B, :T], enc[:B], W, cfg, defect="fc2_bias", layer=1, col0=DEFECT_COL)
+    _, col, tile = dref.worst(bad, rx)
+    print(f"reference defect at 1280: tile {tile:.2e} = {tile / bound:.1f}x the bound {bound:.2e} at columns "
+          f"{col}-{col + 15}")
+    assert col == DEFECT_COL and tile > 3 * bound, (col, tile, bound)
+    return tokens[:B, :T], rx, bound, col, tile
+
+
+@pytest.fixture(scope="module")
+def hidden_engine(gpu):
+    """The engine of hidden_case()'s model (one for every shape: the weights depend on the
+    config and seed alone) and the cases' encoder rows on the device."""
+    cfg, W = hidden_case()[:2]
+    eng = WhisperEngine(cfg, W)
+    on_dev = {}
+
+    def enc_dev(rows, T, n):
+        if (rows, T) not in on_dev:
+            on_dev[rows, T] = torch.from_numpy(hidden_case(rows, T)[3]).to(gpu)
+        return on_dev[rows, T][:n].contiguous()
+
+    return eng, enc_dev
+
+
+def hold_hidden(name, out, T, exact, emu):
+    """x and the caches of a decode_hidden result against the references, row and tile metric,
+    bound K_BOUND x the emulation's own distance; a failure names the worst tile."""
+    got = (out.x.transpose(0, 1), out.kc[:, :, :T], out.vc[:, :, :T])
+    for what, g, r, e in zip(("x", "k cache", "v cache"), got, exact, emu):
+        g = g.double().cpu().numpy()
+        e_row, e_tile = dref.metrics(e, r)
+        g_row, g_tile = dref.metrics(g, r)
+        print(f"hidden 1280 {name} {what}: row {g_row:.2e} tile {g_tile:.2e} | emulation row {e_row:.2e} "
+              f"tile {e_tile:.2e}")
+        at, col, val = dref.worst(g, r)
+        where = f"{name} {what} index {at} (x: row, position; cache: layer, row, slot), columns {col}-{col + 15}"
+        assert np.isfinite(g_tile) and g_tile <= dref.K_BOUND * e_tile, \
+            f"{where}: tile {val:.2e} is {val / (dref.K_BOUND * e_tile):.1f}x the bound {dref.K_BOUND * e_tile:.2e}"
+        assert g_row <= dref.K_BOUND * e_row, \
+            f"{where}: row {g_row:.2e} is {g_row / (dref.K_BOUND * e_row):.1f}x the bound {dref.K_BOUND * e_row:.2e}"
+
+
+HIDDEN_CASES = [(1, 5, 65, 5), (17, 5, 65, 5), (65, 5, 65, 5), (17, 70, 17, 70)]
+
+
+@pytest.mark.parametrize("B,T,rows,Tc", HIDDEN_CASES, ids=[f"rows{c[0]}-T{c[1]}" for c in HIDDEN_CASES])
+def test_decoder_residual_stream_1280(hidden_engine, B, T, rows, Tc):
+    """x after every position and the K / V caches of the launch path at 1, 17 and 65 rows over 5
+    positions (one row, a ragged m-tile, past 64 rows) and at 17 rows over 70 (the decode
+    attention crosses its 64-key round at 20 heads: NR 1 -> 2 inside the call) against
+    decoder_ref.hidden(), row and tile metric, bound K_BOUND x the emulation's own distance on
+    the case's rows (tests/test_decoder_hidden_gpu.py). The plan that ran must be the wide launch
+    path with the absorbed cross-attention, every row on its own encoder row."""
+    eng, enc_dev = hidden_engine
+    _, _, tokens, _, exact, emu = hidden_case(rows, Tc)
+    out = eng.decode_hidden(enc_dev(rows, Tc, B), tokens[:B, :T])
+    want = dict(WIDE_PLAN, B=B, **{"call.enc_rows": 0})
+    assert {k: out.plan[k] for k in want} == want, out.plan
+    cut_ = lambda r: (r[0][:B, :T], r[1][:, :B, :T], r[2][:, :B, :T])
+    hold_hidden(f"rows{B} T{T}", out, T, cut_(exact), cut_(emu))
+
+
+def test_decoder_residual_stream_1280_shared_rows(hidden_engine):
+    """13 rows over 3 encoder rows (5 + 5 + 3), 3 positions: no in-place blocks at 20 heads, the
+    plan must say the rows took gathered copies; row b against hidden() on enc[enc_index[b]]."""
+    eng, enc_dev = hidden_engine
+    tokens, exact, emu = shared_case()
+    B = len(ENC_INDEX)
+    out = eng.decode_hidden(enc_dev(65, 5, 3), tokens, enc_index=ENC_INDEX)
+    want = dict(WIDE_PLAN, B=B, **{"call.enc_rows": GATHERED})
+    assert {k: out.plan[k] for k in want} == want, out.plan
+    hold_hidden("shared rows", out, 3, exact, emu)
+
+
+def test_engine_defect_is_seen_1280(hidden_engine):
+    """The comparison end to end at 1280: an engine whose fc2 bias of layer 1 is zeroed on the
+    last tile (columns 1264 .. 1279, one of 80) lies more than 3x over the bound against the
+    clean reference, at exactly that tile — as the reference with the same defect does
+    (defect_case(), asserted on the CPU first) — and the restored engine is inside the bound."""
+    tokens, rx, bound, _, _ = defect_case()
+    eng, enc_dev = hidden_engine
+    W = hidden_case()[1]
+    B = len(tokens)
+    bad = W[DEFECT_NAME].copy()
+    bad[DEFECT_COL:DEFECT_COL + 16] = 0.0
+    eng.set_tensor(DEFECT_NAME, bad)
+    try:
+        out = eng.decode_hidden(enc_dev(65, 5, B), tokens)
+    finally:
+        eng.set_tensor(DEFECT_NAME, W[DEFECT_NAME])
+    assert {k: out.plan[k] for k in WIDE_PLAN} == WIDE_PLAN, out.plan
+    _, col, tile = dref.worst(out.x.transpose(0, 1).double().cpu().numpy(), rx)
+    print(f"engine defect at 1280: tile {tile:.2e} = {tile / bound:.1f}x the bound at columns {col}-{col + 15}")
+    assert col == DEFECT_COL and tile > 3 * bound, (col, tile, bound)
+    clean = eng.decode_hidden(enc_dev(65, 5, B), tokens)
+    _, col, tile = dref.worst(clean.x.transpose(0, 1).double().cpu().numpy(), rx)
+    print(f"restored engine: worst tile {tile:.2e} = {tile / bound:.2f}x the bound at columns {col}-{col + 15}")
+    assert tile <= bound, (col, tile, bound)

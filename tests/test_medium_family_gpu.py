@@ -281,7 +281,8 @@ def test_vocabulary_projection_history_rules(proj_case, gpu):
 def test_cross_attention_absorbed_1024(gpu, B, Te, nsplit):
     """xattn_kernel<1024, 32> (16 heads in one block's MFMA rows) and the 16-head merge through
     janus_cross_attention_f16: softmax_2(qk_h . enc^T) . enc per head against the float64 torch
-    reference of the same fp16 operands, the bound of the 768 / 1280 cases (3e-3). Key counts
+    reference of the same fp16 operands, the bound of the 768 cases (tests/test_kernels_gpu.py)
+    and of tests/test_large_family_gpu.py::test_cross_attention_absorbed_1280 (3e-3). Key counts
     1500 (46 chunks of 32 + 28), 141 and 77 (ragged last chunks; 77 keys at 8 splits leaves
     splits without keys). Rows that share an encoder row reach this kernel as gathered copies
     (`shared_rows_in_place` is false at 16 heads): the 17-row cases index two encoder rows, and
