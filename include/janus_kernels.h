@@ -133,9 +133,29 @@ int janus_conv1d_f16(const uint16_t* in, int batch, int T_in, int Cin, const uin
                      int padding, int dilation, int transposed, int pre_act, int post_act,
                      const uint16_t* res, int64_t res_bs, float scale, int accumulate,
                      void* stream);
+/* Test entry: janus_conv1d_f16 plus the two launcher arguments only the generator sets.
+ * post_acc_silu: out = silu(out) after the accumulation; remap: the tile order (0 dispatch
+ * order, 1 XCD runs of row blocks, 2 XCD runs over the whole grid, 3 as 2 with the phases of
+ * a row block adjacent, -1 the default) — no order changes any value. */
+int janus_conv1d_f16_ex(const uint16_t* in, int batch, int T_in, int Cin, const uint16_t* packed,
+                        const float* bias, uint16_t* out, int T_out, int Cout, int taps, int stride,
+                        int padding, int dilation, int transposed, int pre_act, int post_act,
+                        const uint16_t* res, int64_t res_bs, float scale, int accumulate,
+                        int post_acc_silu, int remap, void* stream);
+/* Test entry: the generator's tail. x fp16 [B][T][16] -> y = b + sum_{c,j} w[c][j] *
+ * s(x[t + j - 6][c]) (w f32 [16][13], s = SiLU when pre_silu, else identity; zero outside
+ * [0, T)); wav f32 [B][T] = tanh(y), pcm int16 [B][T] = clip(rint(wav * 32767)) (may be
+ * NULL), pre_tanh f32 [B][T] = y (may be NULL). */
+int janus_conv_post_f32(const uint16_t* x, int batch, int T, const float* w, float bias,
+                        int pre_silu, float* wav, int16_t* pcm, float* pre_tanh, void* stream);
+/* Test entry: out [device] int32 [n], out[i] = the logical tile that block i of an n-block
+ * grid takes (the XCD-aware order of the vocoder and GEMM kernels): a permutation of 0..n-1. */
+int janus_xcd_remap_i32(int n, int32_t* out, void* stream);
 
 /*
- * Fused fish-speech ResBlock1 unit for narrow stages (C = 16 or 32, odd k <= 11):
+ * Fused fish-speech ResBlock1 unit (C = 16 or 32 with k in {3, 7, 11} and dilation in
+ * {1, 3, 5}; C = 64, 128 or 256 with odd k <= 11 and (k - 1) * dilation <= 50; any other
+ * (C, k, dilation) is an error):
  * out = (accumulate ? out : 0) + scale * (x + c2(silu(c1(silu(x)) + b1)) + b2), with
  * c1 = Conv1d(C, C, k, dilation, padding dilation*(k-1)/2), c2 = Conv1d(C, C, k,
  * padding (k-1)/2); x/out fp16 [B][T][C] (must not alias); weights packed by
@@ -146,6 +166,13 @@ int janus_resunit_pack(const float* w, uint16_t* packed, int C, int k, void* str
 int janus_resunit_f16(const uint16_t* x, uint16_t* out, const uint16_t* w1, const float* b1,
                       const uint16_t* w2, const float* b2, int batch, int T, int C, int k,
                       int dilation, float scale, int accumulate, void* stream);
+/* Test entry: janus_resunit_f16 plus post_silu (out = silu(out) after the accumulation) and
+ * max_blocks (> 0: at C = 16 / 32 the persistent grid has at most that many blocks, each
+ * walking several tiles; ignored at C >= 64). Any max_blocks gives the same bits. */
+int janus_resunit_f16_ex(const uint16_t* x, uint16_t* out, const uint16_t* w1, const float* b1,
+                         const uint16_t* w2, const float* b2, int batch, int T, int C, int k,
+                         int dilation, float scale, int accumulate, int post_silu, int max_blocks,
+                         void* stream);
 
 /*
  * Decoder cross-attention over the encoder output with absorbed K/V projections:

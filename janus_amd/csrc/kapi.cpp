@@ -8,6 +8,7 @@
 #include "decoder.h"
 #include "dec_persist.h"
 #include "decode_plan.h"
+#include "vocoder.h"
 #include "../../include/janus_kernels.h"
 
 namespace janus {
@@ -217,6 +218,42 @@ extern "C" int janus_conv1d_f16(const uint16_t* in, int batch, int T_in, int Cin
   });
 }
 
+extern "C" int janus_conv1d_f16_ex(const uint16_t* in, int batch, int T_in, int Cin,
+                                   const uint16_t* packed, const float* bias, uint16_t* out, int T_out,
+                                   int Cout, int taps, int stride, int padding, int dilation,
+                                   int transposed, int pre_act, int post_act, const uint16_t* res,
+                                   int64_t res_bs, float scale, int accumulate, int post_acc_silu,
+                                   int remap, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(remap >= -1 && remap <= 3, "conv1d_ex: remap must be -1 .. 3");
+    ConvArgs a = conv_args_torch(
+        reinterpret_cast<const _Float16*>(in), batch, T_in, Cin,
+        reinterpret_cast<const _Float16*>(packed), bias, reinterpret_cast<_Float16*>(out), T_out,
+        Cout, taps, stride, padding, dilation, transposed, pre_act, post_act,
+        reinterpret_cast<const _Float16*>(res), res_bs, scale, accumulate);
+    a.post_acc_silu = post_acc_silu != 0;
+    a.remap = remap;
+    conv_launch(a, (hipStream_t)stream);
+  });
+}
+
+extern "C" int janus_conv_post_f32(const uint16_t* x, int batch, int T, const float* w, float bias,
+                                   int pre_silu, float* wav, int16_t* pcm, float* pre_tanh,
+                                   void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(x && w && wav, "null argument");
+    conv_post_launch(reinterpret_cast<const _Float16*>(x), batch, T, w, bias, wav, pcm,
+                     (hipStream_t)stream, pre_silu != 0, pre_tanh);
+  });
+}
+
+extern "C" int janus_xcd_remap_i32(int n, int32_t* out, void* stream) {
+  return guarded([&] {
+    JANUS_CHECK(out, "null argument");
+    xcd_remap_launch(n, out, (hipStream_t)stream);
+  });
+}
+
 extern "C" int janus_resunit_packed_size(int C, int k) { return resunit_kp(C, k) * C; }
 
 extern "C" int janus_resunit_pack(const float* w, uint16_t* packed, int C, int k, void* stream) {
@@ -236,6 +273,21 @@ extern "C" int janus_resunit_f16(const uint16_t* x, uint16_t* out, const uint16_
     a.w2 = reinterpret_cast<const _Float16*>(w2); a.b2 = b2;
     a.B = batch; a.T = T; a.C = C; a.k = k; a.d = dilation; a.scale = scale;
     a.accumulate = accumulate;
+    resunit_launch(a, (hipStream_t)stream);
+  });
+}
+
+extern "C" int janus_resunit_f16_ex(const uint16_t* x, uint16_t* out, const uint16_t* w1,
+                                    const float* b1, const uint16_t* w2, const float* b2, int batch,
+                                    int T, int C, int k, int dilation, float scale, int accumulate,
+                                    int post_silu, int max_blocks, void* stream) {
+  return guarded([&] {
+    ResUnitArgs a;
+    a.x = reinterpret_cast<const _Float16*>(x); a.out = reinterpret_cast<_Float16*>(out);
+    a.w1 = reinterpret_cast<const _Float16*>(w1); a.b1 = b1;
+    a.w2 = reinterpret_cast<const _Float16*>(w2); a.b2 = b2;
+    a.B = batch; a.T = T; a.C = C; a.k = k; a.d = dilation; a.scale = scale;
+    a.accumulate = accumulate; a.post_silu = post_silu != 0; a.max_blocks = max_blocks;
     resunit_launch(a, (hipStream_t)stream);
   });
 }

@@ -127,6 +127,8 @@ void gemm_i8_launch(int epi, const GemmI8Args& p, hipStream_t s);
 // out[r][:] = fp16( (x[r]-mean)/sqrt(var+eps) * g + b ), x fp32 [rows][d]
 // out[w][k][lane] = mfma.h xshfl<2^k>(in[w][lane]) (kernel test entry)
 void wave_xor_launch(const float* in, float* out, int n_waves, hipStream_t s);
+// out[i] = mfma.h xcd_remap(i, n), i < n (kernel test entry)
+void xcd_remap_launch(int n, int32_t* out, hipStream_t s);
 void layernorm_launch(const float* x, const float* g, const float* b, _Float16* out, int rows,
                       int d, float eps, hipStream_t s);
 // fp32 out variant (final encoder LN keeps fp32 for the cross-attention K/V GEMMs' input)
@@ -230,7 +232,8 @@ struct ConvArgs {
   int B;
   int post_acc_silu = 0;                // out = silu(out) after the accumulation
   int remap = -1;                       // tile order: 0 dispatch, 1 XCD runs of row blocks,
-                                        // 2 XCD runs over the whole grid; -1 = default
+                                        // 2 XCD runs over the whole grid, 3 the same with the
+                                        // phases of a row block adjacent; -1 = default (3)
 };
 // The same products on hipBLASLt (blaslt.cpp), a comparison point only (the product path
 // runs gemm_big): true when the library ran the GEMM (plain and residual epilogues; GELU
@@ -259,9 +262,14 @@ struct ResUnitArgs {
   // out = silu(out) after the accumulation: the last unit of a ParallelBlock stores the
   // SiLU its consumer (the next upsampler, or conv_post) would apply on every read
   int post_silu = 0;
+  // narrow units (C <= 32): cap of the persistent grid, 0 = none (kernel test entry: a few
+  // blocks walk many tiles each)
+  int max_blocks = 0;
 };
 int resunit_kp(int C, int k);
-bool resunit_supported(int C, int k);
+// a fused unit exists for (C, k, d): C <= 32 the compiled k in {3, 7, 11} x d in {1, 3, 5},
+// C >= 64 any odd k <= 11 with (k - 1) * d <= 50
+bool resunit_supported(int C, int k, int d);
 void resunit_pack(const float* w, _Float16* out, int C, int k, hipStream_t s);
 void resunit_launch(const ResUnitArgs& a, hipStream_t s);
 

@@ -107,4 +107,17 @@ void wave_xor_launch(const float* in, float* out, int n_waves, hipStream_t s) {
   JANUS_LAUNCH_CHECK();
 }
 
+// The tile order of mfma.h (xcd_remap) as the kernels compute it: out[i] = xcd_remap(i, n)
+// (janus_xcd_remap_i32, a kernel test entry).
+__global__ __launch_bounds__(256) void xcd_remap_kernel(int n, int32_t* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = xcd_remap(i, n);
+}
+
+void xcd_remap_launch(int n, int32_t* out, hipStream_t s) {
+  if (n <= 0) return;
+  xcd_remap_kernel<<<(n + 255) / 256, 256, 0, s>>>(n, out);
+  JANUS_LAUNCH_CHECK();
+}
+
 }  // namespace janus

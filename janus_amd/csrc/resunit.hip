@@ -339,7 +339,8 @@ static void narrow_cfg(const ResUnitArgs& a, hipStream_t s) {
   // HBM contention with the decoder) better than fewer, longer stripes. Sweep (vocoder
   // side per step): 128 -> +3 ms, 256 -> 315.6, 512 -> 313.5, 1024 -> 312.2, 2048 -> 313,
   // one block per tile -> 327.7 ms.
-  const int grid = std::min(n_tiles, 1024 * per_cu);
+  int grid = std::min(n_tiles, 1024 * per_cu);
+  if (a.max_blocks > 0) grid = std::min(grid, a.max_blocks);  // kernel test entry only
   kern<<<grid, G::NT, G::LDS, s>>>(a, tiles_per_utt, n_tiles);
   JANUS_LAUNCH_CHECK();
 }
@@ -366,13 +367,15 @@ static void narrow_k(const ResUnitArgs& a, hipStream_t s) {
   else throw Error("resunit: k must be 3, 7 or 11 for C <= 32");
 }
 
-bool resunit_supported(int C, int k) {
-  if (C >= 64) return resunit_wide_supported(C, k, 5);
-  return (C == 16 || C == 32) && (k == 3 || k == 7 || k == 11);
+bool resunit_supported(int C, int k, int d) {
+  if (C >= 64) return resunit_wide_supported(C, k, d);
+  return (C == 16 || C == 32) && (k == 3 || k == 7 || k == 11) && (d == 1 || d == 3 || d == 5);
 }
 
 void resunit_launch(const ResUnitArgs& a, hipStream_t s) {
-  JANUS_CHECK(resunit_supported(a.C, a.k), "resunit: C must be 16, 32, 64, 128 or 256, k odd <= 11");
+  JANUS_CHECK(resunit_supported(a.C, a.k, a.d),
+              "resunit: C = 16 / 32 with k in {3, 7, 11}, d in {1, 3, 5}, or C = 64 / 128 / 256 with "
+              "k odd <= 11, (k-1)*d <= 50");
   JANUS_CHECK(a.x != a.out, "resunit: out must not alias x");
   if (a.B <= 0 || a.T <= 0) return;
   if (a.C >= 64) {

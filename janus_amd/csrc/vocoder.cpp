@@ -110,7 +110,7 @@ static void prepare(janus_vocoder* v, hipStream_t s) {
                   k, 1, d * (k - 1) / 2, d, 0, s);
         make_conv(v, v->rb[rb_index(c, i, kj, m, 1)], p + ".convs2." + std::to_string(m), ch, ch,
                   k, 1, (k - 1) / 2, 1, 0, s);
-        if (resunit_supported(ch, k)) {
+        if (resunit_supported(ch, k, d)) {  // else: the conv pair above (forward)
           VUnit& U = v->units[rb_index(c, i, kj, m, 0) / 2];
           U.c = ch; U.k = k; U.d = d;
           const int64_t n = (int64_t)resunit_kp(ch, k) * ch;
